@@ -7,8 +7,14 @@ batch whose inputs are already resident in HBM.  For N>1 each rank owns the
 resources ``res % N == rank`` (hash sharding, no data-path collective) and
 decides its own 2^27-event batch: weak scaling.
 
-Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for the byte
-model behind ``roofline`` and for the cpu_baseline sample.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times
+``--steps`` steps and prints the headline (``value``, ``ms_per_step``);
+``--dump-outputs DIR`` also writes the last timed step's verdicts as .npy
+files.  Everything else -- the roofline, the oracle replays (parity and
+cpu_baseline), the aggregate / metrics.log / degrade legs, the other configs
+and the end-to-end leg -- runs only with ``--full``.  See DESIGN.md
+"Measurement" for the byte model behind ``roofline`` and for the cpu_baseline
+sample.
 """
 import argparse
 import json
@@ -28,6 +34,11 @@ engine.lib()   # the HIP runtime of /opt/rocm is loaded before anything else
 METRIC = "flow-check decisions/sec (node) + % HBM roofline, 10M resources, 1/2/4/8 GPU"
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md)
 DURATION_MS = 4000             # trace time per batch
+STAGE_THREADS = 8              # host threads shifting the timestamps of a staged batch
+RING_BATCHES = 64              # batches resident in HBM at a time (BatchRing)
+DUMP_SAMPLE = 1 << 21          # --dump-outputs: events sampled from a larger batch (32 MB of .npy)
+DUMP_SEED = 20260101
+CHECK_BATCHES = 16             # --full: the oracle replays at most this many batches (checked_run)
 
 
 def log(*a):
@@ -37,10 +48,18 @@ def log(*a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5,
+                    help="timed steps (any number: up to 64 batches are resident in HBM at a time)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--resources", type=int, default=10_000_000)
     ap.add_argument("--events", type=int, default=1 << 27)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline: roofline, oracle replays "
+                         "(parity, cpu_baseline), aggregate / metrics.log / degrade legs, the other configs, the "
+                         "end-to-end leg (N > 1: the SystemRule exchange leg); the --no-* options and --legs trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the verdicts of the last timed step (what the caller of sf_submit receives) as "
+                         "DIR/<name>.npy, float32 / float64 (a fixed, seeded sample of a large batch)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the whole-batch oracle replay (parity + cpu_baseline)")
     ap.add_argument("--no-metric-log", action="store_true")
     ap.add_argument("--no-degrade", action="store_true")
@@ -53,7 +72,7 @@ def main():
                     help="config3_origin leg: the variants to run")
     ap.add_argument("--placement", type=int, default=16384,
                     help="N > 1: move the top-K resources (by the previous batch's counts) across the ranks, LPT "
-                         "greedy (sentinel_amd/placement.py); 0 = every resource at res % N")
+                         "greedy (sentinel_amd/placement.py); 0 = every resource at res %% N")
     ap.add_argument("--no-system-leg", action="store_true", help="N > 1: skip the RCCL SystemRule exchange leg")
     ap.add_argument("--heavy-min", type=int, default=0,
                     help="segments of more events than this go to the heavy kernels (0: the engine default, 512)")
@@ -117,36 +136,47 @@ def main():
     eng.load_flow_rules(rules)
     steps = args.warmup + args.steps
     # the batch resident in HBM once per step: timestamps shifted so that
-    # consecutive batches continue the same trace (every other array shared)
-    base = engine.DeviceBatch(eng, hb)
-    batches = [base] + [engine.DeviceBatch.with_ts(eng, base, hb.ts_ms + k * DURATION_MS) for k in range(1, steps)]
+    # consecutive batches continue the same trace (every other array shared).
+    # Up to RING_BATCHES batches are resident at a time; a longer run brings
+    # the next load in between two timed stretches (BatchRing).
+    ring = BatchRing(eng, hb, min(steps, RING_BATCHES))
+    ring.fill(range(ring.slots))
     out = engine.DeviceVerdicts(eng, hb.n, with_wait=True, with_rule=False)
-    out0 = engine.DeviceVerdicts(eng, hb.n, with_wait=True, with_rule=True)
-    log(f"[rank {rank}] staged {steps} batches in HBM, t={time.time()-t0:.1f}s")
+    out0 = engine.DeviceVerdicts(eng, hb.n, with_wait=True, with_rule=True) if args.full else None
+    log(f"[rank {rank}] staged {ring.slots} of {steps} batches in HBM, t={time.time()-t0:.1f}s")
 
     # batches are enqueued (sf_submit_async): the engine sorts batch k+1 on
     # its sort stream while it decides batch k; decisions stay in batch order.
-    # Batch 0 (fresh engine) keeps its verdicts for the whole-batch parity check.
-    for k in range(args.warmup):
-        eng.submit_device_async(batches[k], out0 if k == 0 else out)
-    eng.sync()
+    # --full: batch 0 (fresh engine) keeps its verdicts for the whole-batch parity check.
+    def run(first, last, timed):
+        """Batches first .. last-1 decided, a load of resident batches at a
+        time: seconds from the first submit of each load to its sync.  A run
+        of up to RING_BATCHES batches is one load."""
+        total = 0.0
+        for a in range(first, last, ring.slots):
+            b = min(last, a + ring.slots)
+            ring.fill(range(a, b))
+            if timed and dist:
+                dist.barrier()
+            eng.sync()
+            start = time.perf_counter()
+            for k in range(a, b):
+                eng.submit_device_async(ring.get(k), out0 if k == 0 and out0 is not None else out)
+            eng.sync()
+            total += time.perf_counter() - start
+            if timed and dist:
+                dist.barrier()
+        return total
+
+    run(0, args.warmup, False)
     eng.set_timing(True)
-    if dist:
-        dist.barrier()
-    eng.sync()
-    start = time.perf_counter()
-    for k in range(args.warmup, steps):
-        eng.submit_device_async(batches[k], out)
-    eng.sync()
-    elapsed = time.perf_counter() - start
-    if dist:
-        dist.barrier()
+    elapsed = run(args.warmup, steps, True)
     st = eng.stats()
-    status = out.status.numpy()
-    n_pass = int(np.isin(status, abi.PASSED).sum())
-    wait = out.wait_ms.numpy()
-    e_wait = int((wait > 0).sum())
     n_seg = int(st.n_segments)
+    # the verdicts of the run's last batch (--full: batch 0 went to out0, and a one-batch run has no other)
+    last = out0 if steps == 1 and out0 is not None else out
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, world, rank)
 
     times = np.array([elapsed], np.float64)
     if dist:
@@ -169,6 +199,45 @@ def main():
                     "ms_per_step": [b[2] for b in box],
                     "max_over_min_ms": round(max(b[2] for b in box) / max(1e-9, min(b[2] for b in box)), 3),
                     "max_over_mean_events": round(max(b[0] for b in box) / (sum(b[0] for b in box) / world), 3)}
+
+    def result_line(pass_fraction=None):
+        """The headline; pass_fraction needs the verdicts on the host (--full)."""
+        return {"metric": METRIC, "value": round(value, 1), "unit": "decisions/s", "n_gpus": world,
+                "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(wall / args.steps * 1e3, 3),
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64",
+                "data": "synthetic",
+                # (the timed steps run in stretches of up to RING_BATCHES pipelined batches)
+                "timed_stretches": -(-args.steps // ring.slots),
+                "config": {"workload": "config3: 10M resources Zipf(1.1), 60% QPS / 10% THREAD / 15% WarmUp / "
+                                       "15% RateLimiter, acquireCount 1 (90%) or 2-5, RT~Exp(20ms) exits",
+                           "resources": R_total, "events_per_batch_per_gpu": hb.n, "entries_per_batch_per_gpu": n_entry,
+                           "resources_touched": n_seg, "pass_fraction": pass_fraction,
+                           "parallelism": f"resource-sharded x{world}",
+                           "placement": None if pl is None else
+                           {"what": "top-K resources by count spread LPT-greedy over the ranks, the rest at res % N "
+                                    "(counts of the previous batch: the bench's batches repeat one trace shifted "
+                                    "in time)", "K": int(pl.moved.size), "engine_rows_per_rank": R_local},
+                           "trace": "one node-wide trace: N config-3 batches of 2^27 events over all 10M resources "
+                                    "(seeds 3..3+N-1, the same 4 s) superposed, rank r deciding res % N == r"
+                                    if world > 1 else "config-3 batch, seed 3", "per_rank": per_rank}}
+
+    if not args.full:
+        # a plain run ends here: the headline of the timed steps and nothing else
+        if rank == 0:
+            print(json.dumps(result_line()), flush=True)
+        ring.free()
+        out.free()
+        eng.close()
+        if dist:
+            dist.destroy_process_group()
+        return
+
+    # (the timed batches' timestamps, 8 B per event and step, leave HBM to the legs' engines)
+    ring.release()
+    status = last.status.numpy()
+    n_pass = int(np.isin(status, abi.PASSED).sum())
+    wait = last.wait_ms.numpy()
+    e_wait = int((wait > 0).sum())
 
     # roofline of the dominant decision kernel: SURVEY.md §8(d) byte model,
     # B = 25 E + 4 E_wait + 12 E_exit + 528 R_touched, restricted to the
@@ -269,7 +338,7 @@ def main():
     want = (lambda nm: not args.legs or nm in args.legs.split(","))
     if run_legs:
         g0 = (out0.status.numpy(), out0.wait_ms.numpy(), out0.rule_idx.numpy())
-        glast = (out.status.numpy(), out.wait_ms.numpy())
+        glast = (last.status.numpy(), last.wait_ms.numpy())
         if want("e2e_pinned"):
             try:
                 t_leg = time.perf_counter()
@@ -281,7 +350,10 @@ def main():
 
     cpu, parity = None, None
     if rank == 0 and world == 1 and not args.no_cpu and args.warmup > 0:
-        cpu, parity = oracle_leg(rules, hb, R_local, out0, out, eng, steps, per_res)
+        if steps <= CHECK_BATCHES:
+            cpu, parity = oracle_leg(rules, hb, R_local, out0, last, eng, steps, per_res)
+        else:
+            cpu, parity = checked_run(cfg, rules, hb, R_local, per_res, out0)
 
     # node-wide ENTRY_NODE over the shards: RCCL all-reduce (off the decision
     # path, after the timed region)
@@ -331,10 +403,7 @@ def main():
     # after the timed region, each on its own engine except e2e)
     if run_legs:
         # the headline engine is released so that each leg has the device to itself
-        for b in batches:
-            b.free()
-        batches = []
-        base = None
+        ring.free()
         out0.free(); out.free()
         eng.close()
         c3_ms = wall / args.steps * 1e3
@@ -364,31 +433,142 @@ def main():
             system_exchange = {"error": str(ex)[:300]}
 
     if rank == 0:
-        line = {"metric": METRIC, "value": round(value, 1), "unit": "decisions/s", "n_gpus": world,
-                "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(wall / args.steps * 1e3, 3),
-                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64",
-                "data": "synthetic",
-                "config": {"workload": "config3: 10M resources Zipf(1.1), 60% QPS / 10% THREAD / 15% WarmUp / "
-                                       "15% RateLimiter, acquireCount 1 (90%) or 2-5, RT~Exp(20ms) exits",
-                           "resources": R_total, "events_per_batch_per_gpu": hb.n, "entries_per_batch_per_gpu": n_entry,
-                           "resources_touched": n_seg, "pass_fraction": round(n_pass / max(1, n_entry), 4),
-                           "parallelism": f"resource-sharded x{world}",
-                           "placement": None if pl is None else
-                           {"what": "top-K resources by count spread LPT-greedy over the ranks, the rest at res % N "
-                                    "(counts of the previous batch: the bench's batches repeat one trace shifted "
-                                    "in time)", "K": int(pl.moved.size), "engine_rows_per_rank": R_local},
-                           "trace": "one node-wide trace: N config-3 batches of 2^27 events over all 10M resources "
-                                    "(seeds 3..3+N-1, the same 4 s) superposed, rank r deciding res % N == r"
-                                    if world > 1 else "config-3 batch, seed 3", "per_rank": per_rank},
-                "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "aggregate": aggregate,
-                "metric_log": metric_log, "degrade": degrade, "system_exchange": system_exchange, **legs}
+        line = result_line(pass_fraction=round(n_pass / max(1, n_entry), 4))
+        line.update({"roofline": roofline, "cpu_baseline": cpu, "parity": parity, "aggregate": aggregate,
+                     "metric_log": metric_log, "degrade": degrade, "system_exchange": system_exchange, **legs})
         print(json.dumps(line), flush=True)
-    for b in batches[1:]:
-        b.free()
-    if base is not None:
-        base.free()
+    ring.free()
     if dist:
         dist.destroy_process_group()
+
+
+class BatchRing:
+    """The run's batches in HBM: batch k is hb at hb.ts_ms + k * DURATION_MS
+    (only the timestamps differ, every other array is batch 0's).  At most
+    ``slots`` batches are resident at a time, batch k in slot k % slots, so the
+    memory a run takes does not grow with its number of steps (8 B per event
+    and resident batch); fill() brings a load of batches in before they are
+    submitted, outside the timed region.  The shifted timestamps are written
+    by a few host threads into two page-locked buffers in turn, one being
+    filled while the other is copied."""
+
+    def __init__(self, eng, hb, slots):
+        from concurrent.futures import ThreadPoolExecutor
+        self.eng, self.hb, self.slots = eng, hb, max(1, slots)
+        self.base = engine.DeviceBatch(eng, hb)
+        self.slot = [self.base] + [None] * (self.slots - 1)
+        self.held = [0] + [-1] * (self.slots - 1)
+        self.pin, self.bufs = engine.PinnedArrays(eng), None
+        cuts = np.linspace(0, hb.n, STAGE_THREADS + 1).astype(np.int64)
+        self.parts = [slice(int(a), int(b)) for a, b in zip(cuts[:-1], cuts[1:])]
+        self.pool = ThreadPoolExecutor(STAGE_THREADS)
+
+    def _shift(self, k, buf):
+        return [self.pool.submit(np.add, self.hb.ts_ms[s], k * DURATION_MS, out=buf[s]) for s in self.parts]
+
+    def fill(self, ks):
+        """Batches ks (at most ``slots`` consecutive ones) resident.  A slot is
+        overwritten only after the engine has finished with what it held."""
+        need = [k for k in ks if self.held[k % self.slots] != k]
+        if not need:
+            return
+        self.eng.sync()
+        if self.bufs is None:
+            self.bufs = [self.pin.array(self.hb.ts_ms.shape, np.int64) for _ in range(2)]
+        pending = self._shift(need[0], self.bufs[0])
+        for i, k in enumerate(need):
+            for f in pending:
+                f.result()
+            buf = self.bufs[i & 1]
+            if i + 1 < len(need):
+                pending = self._shift(need[i + 1], self.bufs[(i + 1) & 1])
+            s = k % self.slots
+            if self.slot[s] is None:
+                self.slot[s] = engine.DeviceBatch.with_ts(self.eng, self.base, buf)      # (a synchronous copy)
+            else:
+                engine._check(engine.lib().sf_memcpy(self.eng.h, self.slot[s].arrays["ts_ms"].ptr, buf.ctypes.data,
+                                                     buf.nbytes, 0))
+            self.held[s] = k
+
+    def get(self, k):
+        assert self.held[k % self.slots] == k, f"batch {k} is not resident"
+        return self.slot[k % self.slots]
+
+    def release(self):
+        """Everything but batch 0's arrays leaves the device (and the host buffers)."""
+        for s in range(1, self.slots):
+            if self.slot[s] is not None:
+                self.slot[s].free()
+            self.slot[s], self.held[s] = None, -1
+        self.pool.shutdown()
+        self.pin.free()
+        self.bufs = None
+
+    def free(self):
+        self.release()
+        self.base.free()
+        self.held[0] = -1
+
+
+def dump_outputs(path, out, world, rank):
+    """What the timed path computed in its last step, as the caller of
+    sf_submit receives it: the status and the wait of every event.  Written as
+    path/<name>.npy (N > 1: <name>_rank<r>.npy, every rank its own shard):
+
+    sample_index   float64  the events sampled: all of a batch of up to
+                            DUMP_SAMPLE events, else DUMP_SAMPLE indices drawn
+                            with a fixed seed (sorted, with repetition)
+    status         float32  sf_verdicts.status of the sampled events
+    wait_ms        float32  sf_verdicts.wait_ms of the sampled events
+    status_counts  float64  [256] events per status value, the whole batch
+    wait_ms_sum    float64  [1] sum of wait_ms, the whole batch"""
+    os.makedirs(path, exist_ok=True)
+    status, wait = out.status.numpy(), out.wait_ms.numpy()
+    n = status.size
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE))
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, a in (("sample_index", idx.astype(np.float64)), ("status", status[idx].astype(np.float32)),
+                    ("wait_ms", wait[idx].astype(np.float32)),
+                    ("status_counts", np.bincount(status, minlength=256).astype(np.float64)),
+                    ("wait_ms_sum", np.array([wait.sum(dtype=np.int64)], np.float64))):
+        np.save(os.path.join(path, name + sfx + ".npy"), a)
+
+
+def checked_run(cfg, rules, hb, R, per_res, timed_out0, n_batches=None):
+    """oracle_leg for a timed run of more than CHECK_BATCHES batches.  The
+    oracle replays every batch of the run it checks, seconds per batch, so the
+    comparison is made on a run of its own: a fresh engine decides the first
+    CHECK_BATCHES batches of the same trace as the timed run does (enqueued
+    back to back, batch 0 keeping its verdicts), and oracle_leg compares batch
+    0, the last of them and the engine's state after it (16 batches: 64 s of
+    trace time, past the wrap of the minute buckets).  The timed run is tied
+    to it through batch 0: its verdicts (timed_out0) must equal this run's."""
+    n_batches = n_batches or CHECK_BATCHES
+    e = engine.FlowEngine(cfg)
+    try:
+        e.load_flow_rules(rules)
+        bl = BatchRing(e, hb, n_batches)
+        bl.fill(range(n_batches))
+        o0 = engine.DeviceVerdicts(e, hb.n, with_wait=True, with_rule=True)
+        o = engine.DeviceVerdicts(e, hb.n, with_wait=True, with_rule=False)
+        for k in range(n_batches):
+            e.submit_device_async(bl.get(k), o0 if k == 0 else o)
+        e.sync()
+        cpu, parity = oracle_leg(rules, hb, R, o0, o, e, n_batches, per_res)
+        parity["run"] = f"a run of its own: the first {n_batches} batches of the timed trace on a fresh engine"
+        tie = {k: int((getattr(timed_out0, k).numpy() != getattr(o0, k).numpy()).sum())
+               for k in ("status", "wait_ms", "rule_idx")}
+        parity["timed_run_batch0_vs_this_run"] = {"mismatches": tie, "exact": all(v == 0 for v in tie.values())}
+        if "exact" in parity:
+            parity["exact"] = bool(parity["exact"] and all(v == 0 for v in tie.values()))
+        ss = parity.get("steady_state") or {}
+        if "what" in ss:
+            ss["what"] = ss["what"].replace("the last timed one", "the last of that run")
+        bl.free()
+        o0.free(); o.free()
+        return cpu, parity
+    finally:
+        e.close()
 
 
 def node_trace(R_total, n, world, rank, dist, placement_k=0):
@@ -1098,7 +1278,9 @@ def e2e_form(hb, rules, R, steps, g0, glast, timed=None, narrow=False):
     index) of batch k-1 overlap.  A fresh engine; the time shift is only the
     batch's ts_base, so every step reuses the same pinned words.  Parity: the
     verdicts of batch 0 and of the last batch equal the headline run's (itself
-    compared with the oracle).  PCIe-inclusive: never the headline."""
+    compared with the oracle, or, for a run of more than CHECK_BATCHES batches,
+    tied through batch 0 to the run that is: checked_run).  PCIe-inclusive:
+    never the headline."""
     e = engine.FlowEngine(abi.default_config(max_resources=R, max_batch=hb.n))
     pin = engine.PinnedArrays(e)
     try:

@@ -1,9 +1,9 @@
 # rocprofv3 passes over the default bench (run on the GPU box from the repo root):
 #   NAME=<dir under gpurun_out>  PMC=1 (add FETCH_SIZE / WRITE_SIZE passes)
-#   BENCH_ARGS (default "--steps 3 --warmup 1 --no-cpu")
+#   BENCH_ARGS (default "--full --steps 3 --warmup 1 --no-cpu")
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 NAME=${NAME:-prof}; OUT=gpurun_out/$NAME; mkdir -p $OUT
-ARGS=${BENCH_ARGS:---steps 3 --warmup 1 --no-cpu}
+ARGS=${BENCH_ARGS:---full --steps 3 --warmup 1 --no-cpu}
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format rocpd -d $OUT/kt -o kt -- python3 bench.py $ARGS \
     > $OUT/bench.json 2> $OUT/bench.err || { echo KT_FAILED; tail $OUT/bench.err; exit 1; }
 cat $OUT/bench.json

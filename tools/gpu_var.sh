@@ -10,7 +10,7 @@ for r in $(seq ${REPS:-2}); do
     i=$((i+1))
     envs=""
     if [ "$spec" != "-" ]; then envs=$(echo "$spec" | tr ',' ' '); fi
-    env $envs timeout -k 10 240 python3 -u bench.py --no-cpu --steps 10 --warmup 3 --no-legs --no-degrade --no-metric-log ${BENCH_ARGS} > $OUT/b_$i.json 2> $OUT/b_$i.err || { echo BENCH_FAILED $spec; tail -20 $OUT/b_$i.err; exit 1; }
+    env $envs timeout -k 10 240 python3 -u bench.py --full --no-cpu --steps 10 --warmup 3 --no-legs --no-degrade --no-metric-log ${BENCH_ARGS} > $OUT/b_$i.json 2> $OUT/b_$i.err || { echo BENCH_FAILED $spec; tail -20 $OUT/b_$i.err; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/b_$i.json')); print('$spec', d['ms_per_step'], d['roofline']['kernels_ms'])"
   done
 done
