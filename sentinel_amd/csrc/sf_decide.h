@@ -613,6 +613,48 @@ SF_HD uint64_t param_run_rule(const ParamTable& pt, uint32_t res, int rule_k, co
     return live;
 }
 
+// ============================================================ sorted events
+// One 32-bit word per event travels through the sort and is all the decide
+// phase keeps of the event's time, flags and acquireCount (PackedEv::meta,
+// Work::s_meta): time offset from the batch's first event (16 bits) | flags
+// (8 bits) << 16 | acquireCount (8 bits) << 24.  Two escapes keep it exact: an
+// offset of PV_DTS_FAR (65,535 ms or more) and a count field of 0 (a count
+// outside 1..255) read the caller's batch through the sort permutation.
+// ev_pack is the only encoder, the ev_* accessors below the only decoders.
+// sr: the planner's mask byte of the event (SYS_NONE: none).
+SF_HD uint32_t ev_pack(int64_t ts, int64_t ts0, uint8_t f, uint8_t sr, int32_t c) {
+    const int64_t d = ts - ts0;
+    const uint32_t dts = (d >= 0 && d < (int64_t)PV_DTS_FAR) ? (uint32_t)d : PV_DTS_FAR;
+    uint32_t fl = f & 0x0Fu;
+    if ((f & (SF_EV_BLOCKED | SF_EV_EXIT)) == SF_EV_BLOCKED)     // blocked by AuthoritySlot (before SystemSlot)
+        fl |= EVF_SYSBLK | ((uint32_t)SYSR_OTHER << EVF_SYSREASON_SHIFT);
+    else if ((f & SF_EV_IN) && !(f & SF_EV_EXIT) && sr < SYS_INERT)   // SystemBlockException forced by the planner
+        fl |= EVF_SYSBLK | ((uint32_t)sr << EVF_SYSREASON_SHIFT);     // (SYS_INERT / SYS_NONE: none)
+    const uint32_t c8 = (c >= 1 && c <= 255) ? (uint32_t)c : 0u;
+    return dts | (fl << 16) | (c8 << 24);
+}
+
+// The sorted events of one (sub-)batch: the words, and what the escapes read
+// (b_ts / b_cnt are the view's own pointers, already offset by its base).
+struct SortedEv {
+    const uint32_t* meta; const uint32_t* perm;
+    const int64_t* b_ts; const int32_t* b_cnt;
+    int64_t t0;                                  // b_ts[0], read once per kernel (ev_open)
+};
+SF_HD void ev_open(SortedEv& e) { e.t0 = e.b_ts[0]; }
+SF_HD uint8_t ev_flags(uint32_t m) { return (uint8_t)(m >> 16); }
+SF_HD int64_t ev_time(const SortedEv& e, uint32_t m, uint32_t j) {
+    const uint32_t d = m & 0xffffu;
+    return d != PV_DTS_FAR ? e.t0 + (int64_t)d : e.b_ts[e.perm[j]];
+}
+SF_HD int32_t ev_count(const SortedEv& e, uint32_t m, uint32_t j) {
+    const uint32_t c8 = m >> 24;
+    return c8 ? (int32_t)c8 : e.b_cnt[e.perm[j]];
+}
+SF_HD int64_t ev_time(const SortedEv& e, uint32_t j) { return ev_time(e, e.meta[j], j); }
+SF_HD int32_t ev_count(const SortedEv& e, uint32_t j) { return ev_count(e, e.meta[j], j); }
+SF_HD uint8_t ev_flags(const SortedEv& e, uint32_t j) { return ev_flags(e.meta[j]); }
+
 // ============================================================ the segment
 struct SegIO {          // sorted-order batch arrays
     const int64_t* ts; const int32_t* cnt; const uint8_t* flags;
@@ -628,7 +670,37 @@ struct SegIO {          // sorted-order batch arrays
     // submission order (read through perm; origin / context may be null)
     const uint32_t* ev_res; const uint32_t* ev_origin; const uint32_t* ev_ctx;
     uint32_t shard_count;
+    // The sorted events.  The device reads nothing else for time, count and
+    // flags; ts / cnt / flags above are the host build's full-width arrays
+    // (tests/hostsim initialises them positionally and leaves ev null).
+    SortedEv ev;
 };
+
+// Time, acquireCount and flags of sorted event j.  ev_word is the one load;
+// the lane walks keep a chunk of words in registers and decode on use.  The
+// host build without words hands out a word whose two escapes are set, and
+// the escapes then read its full-width arrays.
+SF_HD uint32_t ev_word(const SegIO& io, uint32_t j) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+    if (!io.ev.meta) return PV_DTS_FAR | ((uint32_t)io.flags[j] << 16);
+#endif
+    return io.ev.meta[j];
+}
+SF_HD int64_t ev_time(const SegIO& io, uint32_t m, uint32_t j) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+    if (!io.ev.meta) return io.ts[j];
+#endif
+    return ev_time(io.ev, m, j);
+}
+SF_HD int32_t ev_count(const SegIO& io, uint32_t m, uint32_t j) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+    if (!io.ev.meta) return io.cnt[j];
+#endif
+    return ev_count(io.ev, m, j);
+}
+SF_HD int64_t ev_time(const SegIO& io, uint32_t j) { return ev_time(io, ev_word(io, j), j); }
+SF_HD int32_t ev_count(const SegIO& io, uint32_t j) { return ev_count(io, ev_word(io, j), j); }
+SF_HD uint8_t ev_flags(const SegIO& io, uint32_t j) { return ev_flags(ev_word(io, j)); }
 
 // final verdict of sorted event j, straight into the caller's arrays
 // (the status itself stays in sorted order, v_status: launch_scatter moves all
@@ -762,7 +834,7 @@ SF_HD void decide_segment(const DevState& st, const SegIO& io, uint32_t res, uin
     // (each cache line of the sorted arrays is then fetched once, not once per
     // event after the lines of the other lanes' segments evicted it), and picked
     // out of registers by unrolled selects (no dynamic register indexing).
-    int64_t t_[EV_CH]; int32_t c_[EV_CH]; uint8_t f_[EV_CH];
+    uint32_t m_[EV_CH];
     // statuses out eight at a time (decide_qps_segment)
     uint32_t sblk = lo & ~7u;
     uint64_t sbuf = 0;
@@ -780,13 +852,16 @@ SF_HD void decide_segment(const DevState& st, const SegIO& io, uint32_t res, uin
 #pragma unroll
             for (uint32_t q = 0; q < EV_CH; q++) {
                 const uint32_t jj = j + q < hi ? j + q : hi - 1;
-                t_[q] = io.ts[jj]; c_[q] = io.cnt[jj]; f_[q] = io.flags[jj];
+                m_[q] = ev_word(io, jj);
             }
         }
-        int64_t now = t_[0]; int32_t c = c_[0]; uint8_t fl = f_[0];
+        uint32_t m = m_[0];
 #pragma unroll
         for (uint32_t q = 1; q < EV_CH; q++)
-            if (k_ == q) { now = t_[q]; c = c_[q]; fl = f_[q]; }
+            if (k_ == q) m = m_[q];
+        const int64_t now = ev_time(io, m, j);
+        const int32_t c = ev_count(io, m, j);
+        const uint8_t fl = ev_flags(m);
         const uint32_t na = io.arg_slots ? (io.nargs ? io.nargs[j] : io.arg_slots) : 0;
         uint8_t status; int64_t wait = 0; int rule_idx = 0;
 
@@ -794,16 +869,18 @@ SF_HD void decide_segment(const DevState& st, const SegIO& io, uint32_t res, uin
             int64_t ref = io.eref ? io.eref[j] : -1;
             bool blocked; int64_t create_ts;
             if (ref >= 0) {
-                if ((ref < (int64_t)lo || ref >= (int64_t)j || (io.flags[ref] & SF_EV_EXIT))) {   // entry of another resource / order
+                // (a ref outside [lo, j) is not read: it may lie outside the batch)
+                uint32_t mr = (ref >= (int64_t)lo && ref < (int64_t)j) ? ev_word(io, (uint32_t)ref) : m;
+                if (ev_flags(mr) & SF_EV_EXIT) {               // entry of another resource / order
                     *st.err = SF_ERR_INVALID;
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(SF_HOST_DEBUG)
-                    printf("bad ref j=%u ref=%lld lo=%u flags=%d\n", j, (long long)ref, lo, ref>=0? io.flags[ref]:-1);
+                    printf("bad ref j=%u ref=%lld lo=%u flags=%d\n", j, (long long)ref, lo, (int)ev_flags(mr));
 #endif
-                    ref = j;   // treat as this exit's own slot: reads as not blocked below
+                    ref = j; mr = m;   // treat as this exit's own slot: reads as not blocked below
                 }
                 const uint8_t est = ref >= (int64_t)sblk ? (uint8_t)(sbuf >> (8 * (uint32_t)(ref - sblk))) : io.v_status[ref];
                 blocked = ref == (int64_t)j ? true : v_blocked(est);
-                create_ts = io.ts[ref];
+                create_ts = ev_time(io, mr, (uint32_t)ref);
             }
             else { blocked = ref == EREF_DEAD; create_ts = io.cts ? io.cts[j] : now; }
             if (!blocked) {
@@ -905,19 +982,14 @@ SF_HD void decide_qps_segment(const DevState& st, const SegIO& io, uint32_t res,
     NodeWin<MAXS> nd;
     nw_load_row(nd, st, res);
     const double count = st.rdesc[res].count0;
-    // events read QC at a time with every load in flight together (time,
-    // acquireCount and flags), picked out of registers by
-    // unrolled selects: a lane walking a long segment then waits for memory
-    // once per chunk instead of once per event
+    // events read QC words at a time with every load in flight together,
+    // picked out of registers by unrolled selects: a lane walking a long
+    // segment then waits for memory once per chunk instead of once per event
 #ifndef SF_QPS_CH
 #define SF_QPS_CH 16
 #endif
     constexpr uint32_t QC = SF_QPS_CH;
-    static_assert(QC % 4 == 0, "flags are packed four to a register");
-    // times as 32-bit offsets from the chunk's first (a chunk spanning 2^31 ms
-    // or more falls back to per-event loads), flags four to a register
-    int64_t t0_ = 0; uint32_t td_[QC]; int32_t c_[QC]; uint32_t f4_[QC / 4];
-    bool wide_ = false;
+    uint32_t m_[QC];
     uint32_t sblk = lo & ~7u;                                  // 8-aligned block of the buffered statuses
     uint64_t sbuf = 0;
     auto st_flush = [&](uint32_t jend) {                       // statuses [max(lo, sblk), jend)
@@ -927,40 +999,30 @@ SF_HD void decide_qps_segment(const DevState& st, const SegIO& io, uint32_t res,
     for (uint32_t j = lo; j < hi; j++) {
         const uint32_t k_ = (j - lo) % QC;
         if (k_ == 0) {
-            int64_t tt[QC]; uint8_t ff[QC];
 #pragma unroll
             for (uint32_t q = 0; q < QC; q++) {
                 const uint32_t jj = j + q < hi ? j + q : hi - 1;
-                tt[q] = io.ts[jj]; c_[q] = io.cnt[jj]; ff[q] = io.flags[jj];
+                m_[q] = ev_word(io, jj);
             }
-            t0_ = tt[0];
-            wide_ = tt[QC - 1] - t0_ >= (int64_t)0x7fffffff;
-#pragma unroll
-            for (uint32_t q = 0; q < QC; q++) td_[q] = (uint32_t)(tt[q] - t0_);
-#pragma unroll
-            for (uint32_t q = 0; q < QC / 4; q++)
-                f4_[q] = (uint32_t)ff[4 * q] | ((uint32_t)ff[4 * q + 1] << 8) | ((uint32_t)ff[4 * q + 2] << 16) |
-                         ((uint32_t)ff[4 * q + 3] << 24);
         }
-        uint32_t td = td_[0]; int32_t c = c_[0]; uint32_t fw = f4_[0];
+        uint32_t m = m_[0];
 #pragma unroll
         for (uint32_t q = 1; q < QC; q++)
-            if (k_ == q) { td = td_[q]; c = c_[q]; }
-#pragma unroll
-        for (uint32_t q = 1; q < QC / 4; q++)
-            if (k_ / 4 == q) fw = f4_[q];
-        const uint8_t fl = (uint8_t)(fw >> (8 * (k_ % 4)));
-        const int64_t now = wide_ ? io.ts[j] : t0_ + (int64_t)td;
+            if (k_ == q) m = m_[q];
+        const uint8_t fl = ev_flags(m);
+        const int32_t c = ev_count(io, m, j);
+        const int64_t now = ev_time(io, m, j);
         uint8_t status;
         if (fl & SF_EV_EXIT) {                                  // StatisticSlot.exit :134-165
             int64_t ref = io.eref ? io.eref[j] : -1;
             bool blocked; int64_t create_ts;
             if (ref >= 0) {
-                if (ref < (int64_t)lo || ref >= (int64_t)j || (io.flags[ref] & SF_EV_EXIT)) { *st.err = SF_ERR_INVALID; ref = j; }
+                uint32_t mr = (ref >= (int64_t)lo && ref < (int64_t)j) ? ev_word(io, (uint32_t)ref) : m;
+                if (ev_flags(mr) & SF_EV_EXIT) { *st.err = SF_ERR_INVALID; ref = j; mr = m; }
                 // the entry's status: still in the store buffer, or stored
                 const uint8_t est = ref >= (int64_t)sblk ? (uint8_t)(sbuf >> (8 * (uint32_t)(ref - sblk))) : io.v_status[ref];
                 blocked = ref == (int64_t)j ? true : v_blocked(est);
-                create_ts = io.ts[ref];
+                create_ts = ev_time(io, mr, (uint32_t)ref);
             } else {
                 blocked = ref == EREF_DEAD; create_ts = io.cts ? io.cts[j] : now;
             }

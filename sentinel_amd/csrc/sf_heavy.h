@@ -235,9 +235,9 @@ SF_HD void heavy_qps(Team& tm, const DevState& st, const SegIO& io, const HeavyC
 
     uint32_t p = lo;
     while (p < hi) {
-        const int64_t t0 = io.ts[p];
+        const int64_t t0 = ev_time(io, p);
         const int64_t h = t0 / wl, ws = h * wl, hw_end = ws + wl;
-        const uint32_t b = team_first_true(tm, p, hi, [&](uint32_t j) { return io.ts[j] >= hw_end; });
+        const uint32_t b = team_first_true(tm, p, hi, [&](uint32_t j) { return ev_time(io, j) >= hw_end; });
         // second-window roll at t0 (OccupiableBucketLeapArray.currentWindow)
         const int idx = (int)(h % S);
         int64_t cur_pass = 0, p_prev = 0;
@@ -298,10 +298,11 @@ SF_HD void heavy_qps(Team& tm, const DevState& st, const SegIO& io, const HeavyC
             uint32_t j = f + 1;
             while (j < b && (double)(base + passed + 1) <= thr) {      // else no c >= 1 can pass any more
                 j = team_next(tm, j, b, [&](uint32_t k) {
-                    return is_checked_entry(io.flags[k]) && (double)(base + passed + io.cnt[k]) <= thr;
+                    const uint32_t m = ev_word(io, k);
+                    return is_checked_entry(ev_flags(m)) && (double)(base + passed + ev_count(io, m, k)) <= thr;
                 });
                 if (j >= b) break;
-                passed += io.cnt[j];
+                passed += ev_count(io, j);
                 if (tm.leader()) or_bits(hc.passbits + (j >> 6), 1ull << (j & 63));
                 j++;
             }
@@ -329,18 +330,20 @@ SF_HD void heavy_rl(Team& tm, const DevState& st, const SegIO& io, const HeavyCt
         while (p < hi) {
             const int64_t thr = L + cost1 - rule.max_queue_ms;
             // entries before thr cannot pass (cost >= cost1 for c >= 1); first candidate chunk checked directly
-            uint32_t j = (p < hi && io.ts[p] >= thr) ? p
-                         : team_first_true(tm, p, hi, [&](uint32_t k) { return io.ts[k] >= thr; });
+            uint32_t j = (p < hi && ev_time(io, p) >= thr) ? p
+                         : team_first_true(tm, p, hi, [&](uint32_t k) { return ev_time(io, k) >= thr; });
             j = team_next(tm, j, hi, [&](uint32_t k) {
-                if (!is_checked_entry(io.flags[k])) return false;
-                const int32_t c = io.cnt[k];
+                const uint32_t m = ev_word(io, k);
+                if (!is_checked_entry(ev_flags(m))) return false;
+                const int32_t c = ev_count(io, m, k);
                 const int64_t ck = c == 1 ? cost1 : j_round(1.0 * c / rule.count * 1000);
-                return io.ts[k] >= L + ck - rule.max_queue_ms;
+                return ev_time(io, m, k) >= L + ck - rule.max_queue_ms;
             });
             if (j >= hi) break;
-            const int32_t cj = io.cnt[j];
+            const uint32_t mj = ev_word(io, j);
+            const int32_t cj = ev_count(io, mj, j);
             const int64_t cost = cj == 1 ? cost1 : j_round(1.0 * cj / rule.count * 1000);
-            const int64_t t = io.ts[j];
+            const int64_t t = ev_time(io, mj, j);
             int32_t wait = 0;
             if (L + cost <= t) L = t;
             else { L += cost; wait = (int32_t)(L - t); }
@@ -371,8 +374,9 @@ inline void heavy_thread(Team&, const DevState& st, const SegIO& io, const Heavy
     const double M = st.rules[st.rule_off[res]].count;
     int64_t T = st.threads[res];
     for (uint32_t j = lo; j < hi; j++) {
-        if (is_entry(io.flags[j])) {
-            if (!(io.flags[j] & EVF_SYSBLK) && (double)(int32_t)((uint32_t)(int32_t)T + (uint32_t)io.cnt[j]) <= M) {
+        const uint32_t m = ev_word(io, j);
+        if (is_entry(ev_flags(m))) {
+            if (!(ev_flags(m) & EVF_SYSBLK) && (double)(int32_t)((uint32_t)(int32_t)T + (uint32_t)ev_count(io, m, j)) <= M) {
                 T++;
                 hc.passbits[j >> 6] |= 1ull << (j & 63);
             }
@@ -426,8 +430,9 @@ SF_HD void heavy_apply(const DevState& st, const HeavyCtx& hc, uint32_t s, uint3
 struct EvContrib { uint8_t status; int32_t wait; bool touch, passed, live_exit; int64_t c, rt; bool err; };
 SF_HD EvContrib heavy_event(const HeavyCtx& hc, const SegIO& io, uint32_t lo, uint8_t mode, uint32_t j) {
     EvContrib r{};
-    const uint8_t f = io.flags[j];
-    r.c = io.cnt[j];
+    const uint32_t m = ev_word(io, j);
+    const uint8_t f = ev_flags(m);
+    r.c = ev_count(io, m, j);
     const bool all = mode == SM_NORULE;
     if (is_entry(f)) {
         const bool sysb = (f & EVF_SYSBLK) != 0;
@@ -437,11 +442,12 @@ SF_HD EvContrib heavy_event(const HeavyCtx& hc, const SegIO& io, uint32_t lo, ui
         r.touch = true;
     } else {
         const int64_t ref = io.eref ? io.eref[j] : -1;
-        r.live_exit = ref == -1 || (ref >= (int64_t)lo && ref < (int64_t)j && !(io.flags[ref] & EVF_SYSBLK) &&
+        r.live_exit = ref == -1 || (ref >= (int64_t)lo && ref < (int64_t)j && !(ev_flags(io, (uint32_t)ref) & EVF_SYSBLK) &&
                                     (all || pass_bit(hc.passbits, (uint32_t)ref)));
         r.status = r.live_exit ? SF_V_EXIT : SF_V_EXIT_IGNORED;
         r.touch = r.live_exit;
-        r.rt = io.ts[j] - (ref >= 0 ? io.ts[ref] : (io.cts ? io.cts[j] : io.ts[j]));
+        const int64_t now = ev_time(io, m, j);
+        r.rt = now - (ref >= 0 ? ev_time(io, (uint32_t)ref) : (io.cts ? io.cts[j] : now));
         r.err = (f & SF_EV_ERROR) != 0;
     }
     return r;

@@ -173,13 +173,15 @@ struct EntryAcc {
     unsigned int pad;
 };
 
-// 16-B radix-sort payload of one event (batch time span < 2^32 ms)
 // Sort payload, 8 B: submission index, and meta = time offset from the batch's
 // first event (16 bits, PV_DTS_FAR: read the batch's ts) | flags (8 bits) << 16
-// | acquireCount (8 bits, 1..255; 0: read the batch's count) << 24.
+// | acquireCount (8 bits, 1..255; 0: read the batch's count) << 24.  The last
+// sort pass stores meta as it is (Work::s_meta): the decide phase reads time,
+// acquireCount and flags of a sorted event through the ev_* accessors
+// (sf_decide.h), never a full-width sorted copy.
 struct alignas(8) PackedEv { uint32_t idx, meta; };
-// the payload of a batch with origins: the origin id rides along (k_unpack
-// writes it in sorted order for the origin-node pass, sf_origin.hip)
+// the payload of a batch with origins: the origin id rides along (the last
+// sort pass writes it in sorted order for the origin-node pass, sf_origin.hip)
 struct PackedEvO { uint32_t idx, meta, origin; };
 constexpr uint32_t PV_DTS_FAR = 0xffffu;
 
@@ -210,12 +212,12 @@ struct Work {
     uint32_t* keys_in;   uint32_t* keys_out;     // local resource id
     uint32_t* perm;                              // sorted position -> submission index
     PackedEv* pv_in; PackedEv* pv_out;           // sort payload
-    uint32_t* wide;                              // batch times exceed 32-bit offsets (k_unpack reads the batch)
+    uint32_t* wide;                              // (unused)
     int32_t* err;                                // batch error flag (this Work set's batch)
     bool ox_dirty;                               // index pass ran, origin apply (k_ox_reset) not enqueued
     uint32_t* head;      uint32_t* head_scan;    // segment flags and positions
     uint32_t* seg_start; uint32_t* seg_res; uint32_t* n_seg;
-    int64_t* s_ts; int32_t* s_cnt; uint8_t* s_flags;
+    uint32_t* s_meta;                            // PackedEv::meta of each sorted event (SortedEv, sf_decide.h)
     int64_t* s_eref; int64_t* s_cts;
     uint8_t* s_nargs; uint8_t* s_atag; uint64_t* s_abits;  // [slot][n]
     uint8_t* v_status; int32_t* v_wait; uint16_t* v_rule;
@@ -299,7 +301,7 @@ struct DevBatch {
 };
 struct DevVerdicts { uint8_t* status; int32_t* wait; uint16_t* rule; };
 
-// internal event flags (sorted-order s_flags; never set by the caller): a
+// internal event flags (the flag byte of s_meta; never set by the caller): a
 // SystemBlockException forced by the SystemRule planner, reason in bits 4-6
 constexpr uint8_t EVF_SYSBLK = 0x80u;
 constexpr uint8_t EVF_SYSREASON_SHIFT = 4;
@@ -317,8 +319,7 @@ constexpr uint8_t SYSR_OTHER = 7;
 constexpr int64_t EREF_DEAD = -2;
 
 // ---- launchers (sf_kernels.hip) ----
-hipError_t query_temp_bytes(uint32_t max_n, uint32_t key_bits, size_t* sort_bytes, size_t* scan_bytes,
-                            size_t* pscan_bytes);
+hipError_t query_temp_bytes(uint32_t max_n, size_t* sort_bytes, size_t* scan_bytes, size_t* pscan_bytes);
 hipError_t launch_init_state(const DevState& st, hipStream_t s);
 hipError_t launch_rdesc(const DevState& st, hipStream_t s);   // RDesc of every resource from the rule tables
 hipError_t launch_entry_node(const DevState& st, const DevBatch& b, const uint8_t* vstatus, EntryNode* en,

@@ -2,11 +2,12 @@
 //
 // Sort phase (sort stream, one of two Work sets; overlaps the previous
 // batch's decide phase):
-//   k_keys_packed  validate + map resource ids to shard-local keys, 8-B payload
-//   radix sort     stable (key, payload) sort by resource: per-resource time order
-//                  is the input order (LeapArray semantics need it)
-//   head scan      inclusive scan of segment-head flags (segment table written by k_unpack)
-//   k_unpack       events into sorted order (SoA), per-segment flags
+//   radix sort     (sf_rsort.h) validate + map resource ids to shard-local keys, 8-B
+//                  payload; stable (key, payload) sort by resource: per-resource
+//                  time order is the input order (LeapArray semantics need it);
+//                  the last pass leaves keys, submission index and the event's
+//                  32-bit word (time offset, flags, acquireCount) in sorted order
+//   k_segs_*       segment table, head scan, per-segment flags, acquireCount prefix
 //   k_gather_exit  exits: sorted position of the entry (binary search in its segment), exit_of map
 //   pc scan        inclusive prefix of entry acquireCount (heavy window budgets)
 //   k_classify     light segments (by length class) -> lane interpreter; heavy -> window/skip algorithms
@@ -41,122 +42,11 @@ __global__ void k_init_state(DevState st, size_t n_sec, size_t n_min) {
     for (size_t k = i; k < st.R; k += stride) st.threads[k] = 0;
 }
 
-// Sort payload: the radix sort carries each event's index, time offset from
-// the batch's first event, flags and acquireCount packed into 8 bytes
-// (PackedEv), so the sorted order is read back with coalesced loads instead of
-// a random gather from the submission-order arrays; an offset or count that
-// does not fit is read from the batch by k_unpack for that event only.
-template <bool ORG>
-__global__ void k_keys_packed(DevBatch b, uint32_t* keys, void* pvv, uint32_t shard_count, uint32_t shard_index,
-                              uint32_t R, int32_t* err, const int64_t* last_ts, const uint32_t* xmap) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= b.n) return;
-    uint32_t r = b.res[i];
-    uint32_t l = r / shard_count;
-    if (r % shard_count != shard_index || l >= R) { *err = SF_ERR_INVALID; l = 0; }
-    if (xmap) {                                                  // an xflow group is one segment (sf_xflow.h)
-        const uint32_t g = xmap[l];
-        if (g != XNONE) l = g;
-    }
-    // the mocked clock never goes back: within the batch and across batches
-    // (LeapArray would hand such an event a throwaway window)
-    if (b.ts[i] < (i ? b.ts[i - 1] : *last_ts)) *err = SF_ERR_INVALID;
-    keys[i] = l;
-    const int64_t d = b.ts[i] - b.ts[0];
-    const uint32_t dts = (d >= 0 && d < (int64_t)PV_DTS_FAR) ? (uint32_t)d : PV_DTS_FAR;
-    const uint8_t f = b.flags[i];
-    uint32_t fl = f & 0x0Fu;
-    if ((f & (SF_EV_BLOCKED | SF_EV_EXIT)) == SF_EV_BLOCKED)     // blocked by AuthoritySlot (before SystemSlot)
-        fl |= EVF_SYSBLK | ((uint32_t)SYSR_OTHER << EVF_SYSREASON_SHIFT);
-    else if (b.sys && (f & SF_EV_IN) && !(f & SF_EV_EXIT)) {     // SystemBlockException forced by the planner
-        const uint8_t sr = b.sys[i];
-        if (sr < SYS_INERT) fl |= EVF_SYSBLK | ((uint32_t)sr << EVF_SYSREASON_SHIFT);   // (SYS_INERT / SYS_NONE: none)
-    }
-    const int32_t c = b.cnt[i];
-    const uint32_t c8 = (c >= 1 && c <= 255) ? (uint32_t)c : 0u;
-    const uint32_t meta = dts | (fl << 16) | (c8 << 24);
-    if constexpr (ORG) {
-        PackedEvO v; v.idx = i; v.meta = meta; v.origin = b.origin[i];
-        ((PackedEvO*)pvv)[i] = v;
-    } else {
-        PackedEv v; v.idx = i; v.meta = meta;
-        ((PackedEv*)pvv)[i] = v;
-    }
-}
-
-// Also the segment table (segment id of sorted event j = inclusive count of
-// segment heads up to j, minus one): start, resource and the segment count.
-template <bool ORG>
-__global__ void k_unpack(DevBatch b, const void* pvv, const uint32_t* keys, uint32_t* perm, int64_t* s_ts,
-                         int32_t* s_cnt, uint8_t* s_flags, uint8_t* s_nargs, uint8_t* s_atag,
-                         uint64_t* s_abits, const uint32_t* head_scan, uint32_t* seg_start, uint32_t* seg_res,
-                         uint32_t* n_seg, uint32_t* segflag, int64_t* last_ts, const int32_t* err, bool exit_marks,
-                         uint32_t* s_origin, int32_t* prio_seen) {
-    uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= b.n) return;
-    const uint32_t sid = head_scan[j] - 1;
-    if (j == 0 || head_scan[j - 1] != head_scan[j]) { seg_start[sid] = j; seg_res[sid] = keys[j]; }
-    if (j == b.n - 1) { *n_seg = sid + 1; seg_start[sid + 1] = b.n; }
-    if (j == 0 && *err == 0) *last_ts = b.ts[b.n - 1];   // k_keys_packed of this batch has read the old value
-    PackedEv v;
-    if constexpr (ORG) {
-        const PackedEvO vo = ((const PackedEvO*)pvv)[j];
-        v.idx = vo.idx; v.meta = vo.meta;
-        s_origin[j] = vo.origin;
-    } else {
-        v = ((const PackedEv*)pvv)[j];
-    }
-    const uint32_t i = v.idx;
-    const uint32_t dts = v.meta & 0xffffu, c8 = v.meta >> 24;
-    const int32_t c = c8 ? (int32_t)c8 : b.cnt[i];
-    const uint8_t f = (uint8_t)(v.meta >> 16);
-    perm[j] = i;
-    s_ts[j] = dts != PV_DTS_FAR ? b.ts[0] + (int64_t)dts : b.ts[i]; s_cnt[j] = c; s_flags[j] = f;
-    // segment flags (k_classify's routing): the exits (read only by the ParamFlow
-    // routing, heavy_mode), prioritized / non-positive / blocked-before
-    // entries; OR-ed per segment within the wavefront, one atomic per segment
-    // and wavefront (origins need no flag: sf_origin.hip finds them per event)
-    {
-        uint32_t mine = 0;
-        if (exit_marks && (f & SF_EV_EXIT)) mine |= SEGF_EXIT;
-        if (!(f & SF_EV_EXIT))
-            mine |= ((f & SF_EV_PRIO) ? SEGF_PRIO : 0u) | (c <= 0 ? SEGF_NONPOS : 0u) | ((f & EVF_SYSBLK) ? SEGF_SYS : 0u);
-        const unsigned long long any = __ballot(mine != 0);
-        if (any) {
-            const int lane = (int)(threadIdx.x & 63);
-            if (__ballot(mine & SEGF_PRIO) && lane == 0) atomicOr(prio_seen, 1);
-            const int psid = __shfl_up((int)sid, 1);
-            const unsigned long long heads = __ballot(lane == 0 || (uint32_t)psid != sid);
-            const unsigned long long below = (1ull << lane) - 1ull;
-            const unsigned long long after = heads & ~(below | (1ull << lane));
-            const int nxt = after ? __ffsll((long long)after) - 1 : 64;
-            const unsigned long long range = (nxt == 64 ? ~0ull : (1ull << nxt) - 1ull) & ~below;
-            uint32_t acc = 0;
-            const uint32_t kinds[4] = {SEGF_EXIT, SEGF_PRIO, SEGF_NONPOS, SEGF_SYS};
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (__ballot(mine & kinds[k]) & range) acc |= kinds[k];
-            if (((heads >> lane) & 1ull) && acc) atomicOr(&segflag[sid], acc);
-        }
-    }
-    if (b.arg_slots) {
-        if (b.nargs) s_nargs[j] = b.nargs[i];
-        for (uint32_t a = 0; a < b.arg_slots; a++) {
-            const uint8_t tg = b.atag[(size_t)a * b.arg_stride + i];
-            s_atag[(size_t)a * b.n + j] = tg;
-            if (tg == SF_TAG_COLLECTION) atomicOr(&segflag[sid], SEGF_COLL);
-            // a collection argument carries its index into the batch's element CSR
-            s_abits[(size_t)a * b.n + j] = tg == SF_TAG_COLLECTION ? (uint64_t)a * b.arg_stride + (uint64_t)b.base + i
-                                                                  : b.abits[(size_t)a * b.arg_stride + i];
-        }
-    }
-}
-
-// After the hand-written sort (sf_rsort.h), whose last pass wrote the sorted
-// SoA: the segment table (segment id of sorted event j = inclusive count of
+// After the sort (sf_rsort.h), whose last pass wrote the sorted keys, words
+// and arguments: the segment table (segment id of sorted event j = inclusive count of
 // segment heads up to j, minus one: start, resource, count), the engine clock,
 // and the per-segment flags k_classify routes by.
-__global__ void k_segs(DevBatch b, const int32_t* s_cnt, const uint8_t* s_flags, const uint8_t* s_atag,
+__global__ void k_segs(DevBatch b, SortedEv ev, const uint8_t* s_atag,
                        const uint32_t* keys, const uint32_t* head_scan, uint32_t* seg_start, uint32_t* seg_res,
                        uint32_t* n_seg, uint32_t* segflag, int64_t* last_ts, const int32_t* err, bool exit_marks,
                        int32_t* prio_seen) {
@@ -166,8 +56,8 @@ __global__ void k_segs(DevBatch b, const int32_t* s_cnt, const uint8_t* s_flags,
     if (j == 0 || head_scan[j - 1] != head_scan[j]) { seg_start[sid] = j; seg_res[sid] = keys[j]; }
     if (j == b.n - 1) { *n_seg = sid + 1; seg_start[sid + 1] = b.n; }
     if (j == 0 && *err == 0) *last_ts = b.ts[b.n - 1];   // the sort's first pass has read the old value
-    const uint8_t f = s_flags[j];
-    const int32_t c = s_cnt[j];
+    const uint8_t f = ev_flags(ev, j);
+    const int32_t c = (f & SF_EV_EXIT) ? 0 : ev_count(ev, j);
     uint32_t mine = 0;
     if (exit_marks && (f & SF_EV_EXIT)) mine |= SEGF_EXIT;
     if (!(f & SF_EV_EXIT))
@@ -205,39 +95,33 @@ __global__ void k_segs(DevBatch b, const int32_t* s_cnt, const uint8_t* s_flags,
 // (A decoupled look-back single pass measured 5 ms per batch on gfx950: its
 // agent-scope release / acquire publishes write back and bypass the per-XCD
 // L2 on every tile.)
+// the batch's sorted events for a kernel (t0 is read on the device: ev_open)
+static SortedEv sorted_ev(const Work& w, const DevBatch& b) { return SortedEv{w.s_meta, w.perm, b.ts, b.cnt, 0}; }
+
 constexpr int SL_T = 256, SL_K = 16, SL_TILE = SL_T * SL_K;       // 4096 positions per tile
 size_t segs_lb_bytes(uint32_t max_n) { return ((size_t)max_n / SL_TILE + 2) * 16 + 64; }   // (sf_internal.h)
 
 struct SegTile {                 // one thread's 16 positions
     uint32_t k[SL_K];
-    int32_t c[SL_K];
-    uint8_t f[SL_K];
+    uint32_t m[SL_K];            // the events' words (exit flag alone beyond n)
     uint32_t hmask, heads;
     long long acq;
 };
 template <bool PCG>
-__device__ __forceinline__ void seg_load(SegTile& t, const uint32_t* keys, const uint8_t* s_flags, const int32_t* s_cnt,
-                                         uint32_t p0, uint32_t n) {
+__device__ __forceinline__ void seg_load(SegTile& t, const uint32_t* keys, const SortedEv& ev, uint32_t p0, uint32_t n) {
     if (p0 + SL_K <= n) {
         const uint4* kp = (const uint4*)(keys + p0);
 #pragma unroll
         for (int q = 0; q < SL_K / 4; q++) { const uint4 v = kp[q]; t.k[4 * q] = v.x; t.k[4 * q + 1] = v.y; t.k[4 * q + 2] = v.z; t.k[4 * q + 3] = v.w; }
-        const uint4 fv = *(const uint4*)(s_flags + p0);
-        const uint32_t fw[4] = {fv.x, fv.y, fv.z, fv.w};
+        const uint4* mp = (const uint4*)(ev.meta + p0);
 #pragma unroll
-        for (int q = 0; q < SL_K; q++) t.f[q] = (uint8_t)(fw[q >> 2] >> (8 * (q & 3)));
-        if (PCG) {
-            const int4* cp = (const int4*)(s_cnt + p0);
-#pragma unroll
-            for (int q = 0; q < SL_K / 4; q++) { const int4 v = cp[q]; t.c[4 * q] = v.x; t.c[4 * q + 1] = v.y; t.c[4 * q + 2] = v.z; t.c[4 * q + 3] = v.w; }
-        }
+        for (int q = 0; q < SL_K / 4; q++) { const uint4 v = mp[q]; t.m[4 * q] = v.x; t.m[4 * q + 1] = v.y; t.m[4 * q + 2] = v.z; t.m[4 * q + 3] = v.w; }
     } else {
 #pragma unroll
         for (int q = 0; q < SL_K; q++) {
             const bool in = p0 + q < n;
             t.k[q] = in ? keys[p0 + q] : 0u;
-            t.f[q] = in ? s_flags[p0 + q] : (uint8_t)SF_EV_EXIT;
-            t.c[q] = (PCG && in) ? s_cnt[p0 + q] : 0;
+            t.m[q] = in ? ev.meta[p0 + q] : ((uint32_t)SF_EV_EXIT << 16) | (1u << 24);
         }
     }
     const uint32_t kprev = (p0 > 0 && p0 < n) ? keys[p0 - 1] : ~0u;
@@ -248,7 +132,7 @@ __device__ __forceinline__ void seg_load(SegTile& t, const uint32_t* keys, const
         const bool h = in && (p0 + q == 0 || t.k[q] != (q ? t.k[q - 1] : kprev));
         t.hmask |= (h ? 1u : 0u) << q;
         t.heads += h;
-        if (PCG) t.acq += (in && !(t.f[q] & (SF_EV_EXIT | EVF_SYSBLK))) ? (long long)t.c[q] : 0;
+        if (PCG) t.acq += (in && !(ev_flags(t.m[q]) & (SF_EV_EXIT | EVF_SYSBLK))) ? (long long)ev_count(ev, t.m[q], p0 + q) : 0;
     }
 }
 // block-wide exclusive scan of (heads, acq) over the threads; totals out
@@ -279,10 +163,10 @@ __device__ __forceinline__ void seg_block_scan(uint32_t& hx, long long& ax, uint
 }
 
 template <bool PCG>
-__global__ void __launch_bounds__(SL_T) k_segs_red(const uint32_t* keys, const uint8_t* s_flags, const int32_t* s_cnt,
-                                                   uint32_t n, uint32_t* t_heads, long long* t_acq) {
+__global__ void __launch_bounds__(SL_T) k_segs_red(const uint32_t* keys, SortedEv ev, uint32_t n, uint32_t* t_heads,
+                                                   long long* t_acq) {
     SegTile t;
-    seg_load<PCG>(t, keys, s_flags, s_cnt, blockIdx.x * SL_TILE + threadIdx.x * SL_K, n);
+    seg_load<PCG>(t, keys, ev, blockIdx.x * SL_TILE + threadIdx.x * SL_K, n);
     uint32_t hx = t.heads, ht;
     long long ax = t.acq, at;
     seg_block_scan(hx, ax, &ht, &at);
@@ -315,7 +199,7 @@ __global__ void __launch_bounds__(1024) k_segs_tscan(uint32_t* t_heads, long lon
 }
 
 template <bool PCG>
-__global__ void __launch_bounds__(SL_T) k_segs_out(DevBatch b, const int32_t* s_cnt, const uint8_t* s_flags,
+__global__ void __launch_bounds__(SL_T) k_segs_out(DevBatch b, SortedEv ev,
                                                    const uint8_t* s_atag, const uint32_t* keys, uint32_t* head_scan,
                                                    int64_t* pcg, uint32_t* seg_start, uint32_t* seg_res,
                                                    uint32_t* n_seg, uint32_t* segflag, int64_t* last_ts,
@@ -323,7 +207,7 @@ __global__ void __launch_bounds__(SL_T) k_segs_out(DevBatch b, const int32_t* s_
                                                    const uint32_t* t_heads, const long long* t_acq) {
     const uint32_t n = b.n, p0 = blockIdx.x * SL_TILE + threadIdx.x * SL_K;
     SegTile t;
-    seg_load<PCG>(t, keys, s_flags, s_cnt, p0, n);
+    seg_load<PCG>(t, keys, ev, p0, n);
     uint32_t hx = t.heads, ht;
     long long ax = t.acq, at;
     seg_block_scan(hx, ax, &ht, &at);
@@ -348,15 +232,16 @@ __global__ void __launch_bounds__(SL_T) k_segs_out(DevBatch b, const int32_t* s_
             seg_res[hs - 1] = t.k[q];
         }
         hsv[q] = hs;
-        if (PCG) { run += (in && !(t.f[q] & (SF_EV_EXIT | EVF_SYSBLK))) ? (long long)t.c[q] : 0; pv[q] = run; }
+        const uint8_t fq = ev_flags(t.m[q]);
+        // (the count escape is a gather: only events that need the count take it)
+        const int32_t cq = (in && !(fq & SF_EV_EXIT)) ? ev_count(ev, t.m[q], p) : 0;
+        if (PCG) { run += (fq & EVF_SYSBLK) ? 0 : (long long)cq; pv[q] = run; }
         if (!in) continue;
         uint32_t mine = 0;
-        if (exit_marks && (t.f[q] & SF_EV_EXIT)) mine |= SEGF_EXIT;
-        if (!(t.f[q] & SF_EV_EXIT)) {
-            const int32_t cq = PCG ? t.c[q] : s_cnt[p];
-            mine |= ((t.f[q] & SF_EV_PRIO) ? SEGF_PRIO : 0u) | (cq <= 0 ? SEGF_NONPOS : 0u) |
-                    ((t.f[q] & EVF_SYSBLK) ? SEGF_SYS : 0u);
-        }
+        if (exit_marks && (fq & SF_EV_EXIT)) mine |= SEGF_EXIT;
+        if (!(fq & SF_EV_EXIT))
+            mine |= ((fq & SF_EV_PRIO) ? SEGF_PRIO : 0u) | (cq <= 0 ? SEGF_NONPOS : 0u) |
+                    ((fq & EVF_SYSBLK) ? SEGF_SYS : 0u);
         for (uint32_t a = 0; a < b.arg_slots; a++)
             if (s_atag[(size_t)a * n + p] == SF_TAG_COLLECTION) mine |= SEGF_COLL;
         acc |= mine;
@@ -389,9 +274,10 @@ static void launch_segs3(const DevState& st, Work& w, const DevBatch& b, hipStre
     const uint32_t n = b.n, tiles = (n + SL_TILE - 1) / SL_TILE;
     uint32_t* th = (uint32_t*)w.segs_lb;
     long long* ta = (long long*)((char*)w.segs_lb + (((size_t)tiles * 4 + 15) & ~(size_t)15));
-    hipLaunchKernelGGL(k_segs_red<PCG>, dim3(tiles), dim3(SL_T), 0, s, w.keys_out, w.s_flags, w.s_cnt, n, th, ta);
+    const SortedEv ev = sorted_ev(w, b);
+    hipLaunchKernelGGL(k_segs_red<PCG>, dim3(tiles), dim3(SL_T), 0, s, w.keys_out, ev, n, th, ta);
     hipLaunchKernelGGL(k_segs_tscan, dim3(1), dim3(1024), 0, s, th, ta, tiles);
-    hipLaunchKernelGGL(k_segs_out<PCG>, dim3(tiles), dim3(SL_T), 0, s, b, w.s_cnt, w.s_flags, w.s_atag, w.keys_out,
+    hipLaunchKernelGGL(k_segs_out<PCG>, dim3(tiles), dim3(SL_T), 0, s, b, ev, w.s_atag, w.keys_out,
                        w.head_scan, w.pcg, w.seg_start, w.seg_res, w.n_seg, w.segflag, st.last_ts, st.err,
                        st.n_prule != 0, st.prio_seen, th, ta);
 }
@@ -406,11 +292,11 @@ struct HeadFlag {       // 1 where a new resource segment starts in the sorted k
 // entry is found by a binary search of the segment's submission indices (no
 // inverse permutation scattered over the whole batch).  Forward map exit_of
 // for THREAD-grade liveness; s_cts for entries of earlier batches.
-__global__ void k_gather_exit(DevBatch b, const uint32_t* perm, const uint8_t* s_flags,
+__global__ void k_gather_exit(DevBatch b, const uint32_t* perm, const uint32_t* s_meta,
                               const uint32_t* head_scan, const uint32_t* seg_start, int64_t* s_eref,
                               int64_t* s_cts, uint32_t* exit_of, int32_t* err) {
     uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= b.n || !(s_flags[j] & SF_EV_EXIT)) return;
+    if (j >= b.n || !(ev_flags(s_meta[j]) & SF_EV_EXIT)) return;
     const uint32_t i = perm[j];
     const int64_t raw = b.eref[i];
     // -1: the entry passed before this batch (live, create_ts gives its time);
@@ -446,9 +332,10 @@ __global__ void k_gather_exit(DevBatch b, const uint32_t* perm, const uint8_t* s
 }
 
 struct EntryCount {     // acquireCount of the entries the controllers see (input of the pc scan):
-    const int32_t* cnt; const uint8_t* flags;    // 0 for exits and EVF_SYSBLK entries
+    SortedEv ev;                                 // 0 for exits and EVF_SYSBLK entries
     __device__ int64_t operator()(uint32_t j) const {
-        return (flags[j] & (SF_EV_EXIT | EVF_SYSBLK)) ? 0 : (int64_t)cnt[j];
+        const uint32_t m = ev.meta[j];
+        return (ev_flags(m) & (SF_EV_EXIT | EVF_SYSBLK)) ? 0 : (int64_t)ev_count(ev, m, j);
     }
 };
 
@@ -467,7 +354,8 @@ __device__ uint32_t wave_append(uint32_t* counter, bool take) {
 
 // Route each segment: light lane interpreter, heavy window algorithms, or the
 // heavy generic interpreter (one lane of a wavefront).
-__global__ void k_classify(DevState st, Work w, const int64_t* s_ts) {
+__global__ void k_classify(DevState st, Work w, SortedEv ev) {
+    ev_open(ev);
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = s < *w.n_seg;
     uint32_t lo = 0, hi = 0, res = 0;
@@ -485,7 +373,7 @@ __global__ void k_classify(DevState st, Work w, const int64_t* s_ts) {
     // a ParamFlow-only segment of more than 32 events is faster on the
     // wavefront-by-value path (SM_PARAM) than as one lane's serial table walk
     if (light && hi - lo > 32 && (st.rdesc[res].flags & RD_PRULE) &&
-        heavy_mode(st, res, w.segflag[s], s_ts[lo]) == SM_PARAM)
+        heavy_mode(st, res, w.segflag[s], ev_time(ev, lo)) == SM_PARAM)
         light = false;
     // light list slot: workgroup histogram of the length classes in LDS, one
     // global atomic per class and workgroup
@@ -538,10 +426,12 @@ __global__ void k_classify(DevState st, Work w, const int64_t* s_ts) {
     if (!__ballot(heavy)) return;
     uint8_t mode = SM_GENERIC;
     if (heavy) {
-        mode = heavy_mode(st, res, w.segflag[s], s_ts[lo]);
+        const int64_t tlo = ev_time(ev, lo);
+        mode = heavy_mode(st, res, w.segflag[s], tlo);
         if (mode != SM_GENERIC) {
-            const int64_t h0 = s_ts[lo] / st.wl, h1 = s_ts[hi - 1] / st.wl;
-            const int64_t s0 = s_ts[lo] / 1000, s1 = s_ts[hi - 1] / 1000;
+            const int64_t thi = ev_time(ev, hi - 1);
+            const int64_t h0 = tlo / st.wl, h1 = thi / st.wl;
+            const int64_t s0 = tlo / 1000, s1 = thi / 1000;
             const int64_t nh = h1 - h0 + 1, ns = s1 - s0 + 1;
             if (nh > 65536 || ns > 65536) mode = SM_GENERIC;
             else {
@@ -599,6 +489,7 @@ struct LightLists { const uint32_t* list; const uint32_t* counts; uint32_t off[L
 template <int MAXS, bool PF>
 __global__ void __launch_bounds__(128, PF ? SF_LIGHT_MINB : SF_LIGHT_NOPF_MINB) k_decide_light(DevState st, SegIO io, const uint32_t* seg_start,
                                                       const uint32_t* seg_res, LightLists ll) {
+    ev_open(io.ev);
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     int c = LCLS - 1;
     for (; c >= 0; c--) {
@@ -616,6 +507,7 @@ __global__ void __launch_bounds__(128, PF ? SF_LIGHT_MINB : SF_LIGHT_NOPF_MINB) 
 template <int MAXS>
 __global__ void __launch_bounds__(128) k_decide_light_qps(DevState st, SegIO io, const uint32_t* seg_start,
                                                           const uint32_t* seg_res, LightLists ll) {
+    ev_open(io.ev);
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     int c = LCLS - 1;
     for (; c >= 0; c--) {
@@ -634,6 +526,7 @@ template <int MAXS, bool PF>
 __global__ void __launch_bounds__(128, PF ? SF_LIGHT_MINB : SF_LIGHT_NOPF_MINB) k_decide_short(DevState st, SegIO io, const uint32_t* seg_start,
                                                       const uint32_t* seg_res, LightLists ll,
                                                       const uint32_t* n_short) {
+    ev_open(io.ev);
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_short[0]) return;
     const uint32_t s = ll.list[ll.off[0] + t];
@@ -646,6 +539,7 @@ template <int MAXS>
 __global__ void __launch_bounds__(64) k_decide_x(DevState st, SegIO io, const uint32_t* seg_start,
                                                  const uint32_t* seg_res, const uint8_t* seg_mode,
                                                  const uint32_t* n_seg) {
+    ev_open(io.ev);
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= *n_seg || seg_mode[s] != SM_XFLOW) return;
     if (xw_take(st, seg_res[s], seg_start[s + 1] - seg_start[s])) return;
@@ -1052,7 +946,8 @@ struct XwEv {
 };
 __device__ __forceinline__ void xw_ld1(const SegIO& io, uint32_t j, uint32_t hi, XwEv& e) {
     if (j < hi) {
-        e.t = io.ts[j]; e.fl = io.flags[j]; e.c = io.cnt[j]; e.i = io.perm[j];
+        const uint32_t m = ev_word(io, j);
+        e.t = ev_time(io, m, j); e.fl = ev_flags(m); e.c = ev_count(io, m, j); e.i = io.perm[j];
         e.ref = io.eref ? io.eref[j] : -1;
     } else {
         e.t = INT64_MAX; e.fl = 0; e.c = 0; e.i = 0; e.ref = -1;
@@ -1064,7 +959,8 @@ __device__ __forceinline__ void xw_ld2(const SegIO& io, uint32_t j, uint32_t lo,
     if (io.ev_origin) e.origin = io.ev_origin[e.i];
     if (e.fl & SF_EV_EXIT) {
         if (e.ref >= (int64_t)lo && e.ref < (int64_t)j) {
-            e.rfl = io.flags[e.ref]; e.rts = io.ts[e.ref];
+            const uint32_t mr = ev_word(io, (uint32_t)e.ref);
+            e.rfl = ev_flags(mr); e.rts = ev_time(io, mr, (uint32_t)e.ref);
             if (e.ref < (int64_t)jd) e.rvs = io.v_status[e.ref];
         } else if (e.ref < 0 && io.cts) {
             e.cts = io.cts[j];
@@ -1082,6 +978,7 @@ template <int MAXS>
 __global__ void __launch_bounds__(64) k_decide_xw(DevState st, SegIO io, const uint32_t* seg_start,
                                                   const uint32_t* seg_res, const uint32_t* list,
                                                   const uint32_t* n_list) {
+    ev_open(io.ev);
     __shared__ __align__(16) unsigned char snap_raw[sizeof(NodeWin<MAXS>)];
     __shared__ uint8_t cls[64];
     __shared__ uint8_t vch[64];                             // the previous chunk's final statuses
@@ -1371,6 +1268,7 @@ template <int MAXS>
 __global__ void __launch_bounds__(128) k_decide_short_qps(DevState st, SegIO io, const uint32_t* seg_start,
                                                           const uint32_t* seg_res, LightLists ll,
                                                           const uint32_t* n_short) {
+    ev_open(io.ev);
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_short[1]) return;
     const uint32_t s = ll.list[ll.off[0] + ll.cap[0] - 1 - t];
@@ -1421,12 +1319,13 @@ __device__ void heavy_param(const DevState& st, const SegIO& io, const HeavyCtx&
         const uint32_t j = q + (uint32_t)lane;
         const bool valid = j < hi;
         const uint32_t jc = valid ? j : hi - 1;
-        const int64_t now = io.ts[jc];
-        const int32_t c = io.cnt[jc];
+        const uint32_t mw = ev_word(io, jc);
+        const int64_t now = ev_time(io, mw, jc);
+        const int32_t c = ev_count(io, mw, jc);
         const uint32_t na = io.arg_slots ? (io.nargs ? io.nargs[jc] : io.arg_slots) : 0;
         uint32_t tag = SF_TAG_NULL; uint64_t bits = 0;
         if ((int32_t)na > pidx) { tag = io.atag[(size_t)pidx * io.n + jc]; bits = io.abits[(size_t)pidx * io.n + jc]; }
-        const bool sysb = valid && (io.flags[jc] & EVF_SYSBLK);   // blocked before ParamFlowSlot
+        const bool sysb = valid && (ev_flags(mw) & EVF_SYSBLK);   // blocked before ParamFlowSlot
         const bool key = valid && !sysb && tag != SF_TAG_NULL;  // a null value skips every rule (passCheck :53-60)
         s_now[lane] = now; s_c[lane] = c; s_wait[lane] = 0; s_rule[lane] = 0; s_ok[lane] = 0;
         // the lanes of each distinct value: `mine` on the value's first lane
@@ -1472,6 +1371,7 @@ __device__ void heavy_param(const DevState& st, const SegIO& io, const HeavyCtx&
 // run in k_heavy_stream (sf_stream.h).
 template <int MAXS>
 __global__ void __launch_bounds__(64) k_heavy_decide(DevState st, SegIO io, HeavyCtx hc) {
+    ev_open(io.ev);
     // grid-stride over the list (medium ParamFlow segments can outnumber the
     // grid sized for segments above heavy_min); long segments are listed first
     uint32_t s;
@@ -1633,7 +1533,7 @@ __global__ void __launch_bounds__(1024) k_fill_tiles(HeavyCtx hc, StreamCtx sc, 
 // other events (sf_stream.h run mode).
 //   k_thr_heads  run heads of each tile; the segment flag of an acquireCount
 //                beyond THR_CBIG
-__global__ void __launch_bounds__(256) k_thr_heads(const uint8_t* flags, const int32_t* cnt, HeavyCtx hc,
+__global__ void __launch_bounds__(256) k_thr_heads(SortedEv ev, HeavyCtx hc,
                                                    const uint2* tiles, const uint32_t* ntiles, uint32_t* tile_rc,
                                                    uint32_t* segflag) {
     __shared__ uint32_t heads;
@@ -1648,10 +1548,10 @@ __global__ void __launch_bounds__(256) k_thr_heads(const uint8_t* flags, const i
         uint32_t nh = 0;
         bool big = false;
         for (uint32_t j = max(tl.y * FILL_TILE, lo) + threadIdx.x; j < min(tl.y * FILL_TILE + FILL_TILE, hi); j += 256) {
-            const uint8_t f = flags[j];
-            const bool ent = is_checked_entry(f);
-            if (ent) big |= cnt[j] > THR_CBIG;
-            nh += (j == lo || ent != is_checked_entry(flags[j - 1])) ? 1u : 0u;
+            const uint32_t m = ev.meta[j];
+            const bool ent = is_checked_entry(ev_flags(m));
+            if (ent) big |= ev_count(ev, m, j) > THR_CBIG;
+            nh += (j == lo || ent != is_checked_entry(ev_flags(ev, j - 1))) ? 1u : 0u;
         }
         if (__ballot(big) && (threadIdx.x & 63) == 0) atomicOr(&segflag[s], SEGF_BIGC);
         nh = (uint32_t)wave_sum(nh);
@@ -1691,7 +1591,7 @@ __global__ void __launch_bounds__(1024) k_thr_rscan(uint32_t* tile_rc, const uin
     }
 }
 
-__global__ void __launch_bounds__(256) k_thr_rid(const uint8_t* flags, HeavyCtx hc, const uint2* tiles,
+__global__ void __launch_bounds__(256) k_thr_rid(SortedEv ev, HeavyCtx hc, const uint2* tiles,
                                                  const uint32_t* ntiles, const uint32_t* tile_rb) {
     __shared__ uint32_t wsum[4];
     constexpr uint32_t PER = FILL_TILE / 256;
@@ -1707,7 +1607,7 @@ __global__ void __launch_bounds__(256) k_thr_rid(const uint8_t* flags, HeavyCtx 
 #pragma unroll
         for (uint32_t k = 0; k < PER; k++) {
             const uint32_t j = base + k;
-            if (j >= lo && j < hi && (j == lo || is_checked_entry(flags[j]) != is_checked_entry(flags[j - 1])))
+            if (j >= lo && j < hi && (j == lo || is_checked_entry(ev_flags(ev, j)) != is_checked_entry(ev_flags(ev, j - 1))))
                 hm |= 1u << k;
         }
         const uint32_t c = (uint32_t)__popc(hm);
@@ -1729,7 +1629,7 @@ __global__ void __launch_bounds__(256) k_thr_rid(const uint8_t* flags, HeavyCtx 
     }
 }
 
-__global__ void __launch_bounds__(256) k_thr_rec(const uint8_t* flags, const int32_t* cnt, const int64_t* eref,
+__global__ void __launch_bounds__(256) k_thr_rec(SortedEv ev, const int64_t* eref,
                                                  HeavyCtx hc, const uint2* tiles, const uint32_t* ntiles,
                                                  const uint32_t* segflag) {
     const uint32_t nt = ntiles[1];
@@ -1740,18 +1640,19 @@ __global__ void __launch_bounds__(256) k_thr_rec(const uint8_t* flags, const int
         const uint32_t lo = hc.seg_start[s], hi = hc.seg_start[s + 1];
         const bool runs = thr_run_mode(hc, s, lo, hi, segflag[s]);
         for (uint32_t j = max(tl.y * FILL_TILE, lo) + threadIdx.x; j < min(tl.y * FILL_TILE + FILL_TILE, hi); j += 256) {
-            const uint8_t f = flags[j];
+            const uint32_t m = ev.meta[j];
+            const uint8_t f = ev_flags(m);
             if (runs) {
                 if (is_checked_entry(f)) {
                     const uint32_t x = hc.exit_of[j];
-                    hc.rrec[j] = make_uint2(x < hi ? hc.rid[x] : XO_NONE, (uint32_t)cnt[j]);
+                    hc.rrec[j] = make_uint2(x < hi ? hc.rid[x] : XO_NONE, (uint32_t)ev_count(ev, m, j));
                 } else if ((f & SF_EV_EXIT) && (eref ? eref[j] : -1) == -1) {
                     atomicAdd(&hc.run_pre[hc.rid[j]], 1u);      // its entry passed before this batch: live
                 }
                 continue;
             }
             uint2 r;
-            if (is_checked_entry(f)) { r.x = hc.exit_of[j]; r.y = (uint32_t)cnt[j]; }
+            if (is_checked_entry(f)) { r.x = hc.exit_of[j]; r.y = (uint32_t)ev_count(ev, m, j); }
             else if (!(f & SF_EV_EXIT)) { r.x = 0u; r.y = THR_REC_EXIT; }   // blocked before: a no-op (dead exit)
             else {
                 const int64_t ref = eref ? eref[j] : -1;
@@ -1809,7 +1710,7 @@ __device__ __forceinline__ void lds_acc_flush(LdsAcc& A, Acc* table, uint32_t ba
 }
 
 constexpr int FG = (int)FILL_TILE / 256;         // events per lane
-struct FillGrp { uint8_t f[FG]; int32_t c[FG]; int64_t t[FG]; };
+struct FillGrp { uint32_t m[FG]; uint8_t f[FG]; int32_t c[FG]; int64_t t[FG]; };
 
 // vector copy of an aligned group: 16-byte accesses (8-byte for an 8-byte group)
 __device__ __forceinline__ void load16(void* dst, const void* src, int bytes) {
@@ -1830,6 +1731,7 @@ __device__ __forceinline__ void store16(void* dst, const void* src, int bytes) {
 #endif
 __global__ void __launch_bounds__(256, SF_FILL_MINB) k_heavy_fill(DevState st, SegIO io, HeavyCtx hc, const uint2* tiles,
                                                     const uint32_t* ntiles, int cls) {
+    ev_open(io.ev);
     __shared__ LdsAcc acc_h, acc_s;
     const uint32_t NONE = 0xffffffffu;
     const uint32_t nt = ntiles[cls];
@@ -1848,15 +1750,15 @@ __global__ void __launch_bounds__(256, SF_FILL_MINB) k_heavy_fill(DevState st, S
         const uint32_t hwb = hc.acc_hw_base[s], secb = hc.acc_sec_base[s];
         const int64_t hw0 = hc.seg_hw0[s], sec0 = hc.seg_sec0[s];
         const int64_t bh = hw0 * st.wl, bs = sec0 * 1000;
-        const bool rel32 = io.ts[hi - 1] - bs < (int64_t)0xffffffffLL;   // window keys by 32-bit division
+        const bool rel32 = ev_time(io, hi - 1) - bs < (int64_t)0xffffffffLL;   // window keys by 32-bit division
         auto key_of = [&](int64_t tj, uint32_t& kh_, uint32_t& ks_) {
             if (rel32) { kh_ = hwb + (uint32_t)(tj - bh) / wl; ks_ = secb + (uint32_t)(tj - bs) / 1000u; }
             else { kh_ = hwb + (uint32_t)(tj / st.wl - hw0); ks_ = secb + (uint32_t)(tj / 1000 - sec0); }
         };
         // the tile's window rows; a range that leaves the LDS tables flushes them first
         uint32_t th0, ts0, th1, ts1;
-        key_of(io.ts[max(tl.y * FILL_TILE, lo)], th0, ts0);
-        key_of(io.ts[min(tl.y * FILL_TILE + FILL_TILE, hi) - 1], th1, ts1);
+        key_of(ev_time(io, max(tl.y * FILL_TILE, lo)), th0, ts0);
+        key_of(ev_time(io, min(tl.y * FILL_TILE + FILL_TILE, hi) - 1), th1, ts1);
         const bool wide = th1 - th0 >= (uint32_t)ACC_K || ts1 - ts0 >= (uint32_t)ACC_K;
         if (wide || bh_k == NONE || th0 < bh_k || th1 >= bh_k + ACC_K || ts0 < bs_k || ts1 >= bs_k + ACC_K) {
             __syncthreads();
@@ -1873,18 +1775,25 @@ __global__ void __launch_bounds__(256, SF_FILL_MINB) k_heavy_fill(DevState st, S
         FillGrp g;
         int32_t wt[FG];
         if (full) {
-            load16(g.f, io.flags + base, FG); load16(g.c, io.cnt + base, FG * 4); load16(g.t, io.ts + base, FG * 8);
+            load16(g.m, io.ev.meta + base, FG * 4);
             if (rl || prm) load16(wt, io.v_wait + base, FG * 4);
         } else {
 #pragma unroll
             for (int k = 0; k < FG; k++) {
                 const uint32_t j = base + (uint32_t)k;
                 const bool in = j >= a && j < b;
-                g.f[k] = in ? io.flags[j] : (uint8_t)0;
-                g.c[k] = in ? io.cnt[j] : 0;
-                g.t[k] = in ? io.ts[j] : 0;
+                g.m[k] = in ? ev_word(io, j) : PV_DTS_FAR;
                 wt[k] = (in && (rl || prm)) ? io.v_wait[j] : 0;
             }
+        }
+        // decode (events outside the tile's part of the segment: no flags, count and time 0)
+#pragma unroll
+        for (int k = 0; k < FG; k++) {
+            const uint32_t j = base + (uint32_t)k;
+            const bool in = j >= a && j < b;
+            g.f[k] = in ? ev_flags(g.m[k]) : (uint8_t)0;
+            g.c[k] = in ? ev_count(io, g.m[k], j) : 0;
+            g.t[k] = in ? ev_time(io, g.m[k], j) : 0;
         }
         const unsigned long long pw = hc.passbits[base >> 6];
         uint32_t sysm = 0;                                 // entries blocked before the controllers (EVF_SYSBLK)
@@ -1915,8 +1824,9 @@ __global__ void __launch_bounds__(256, SF_FILL_MINB) k_heavy_fill(DevState st, S
                 const int64_t r = ((exm >> k) & 1u) ? rf[k] : -1;
                 const uint32_t rc = r >= 0 && r < (int64_t)io.n ? (uint32_t)r : base;
                 rw[k] = hc.passbits[rc >> 6];
-                rts[k] = r >= 0 ? io.ts[rc] : (io.cts ? io.cts[base + k] : g.t[k]);
-                rfl[k] = io.flags[rc];
+                const uint32_t mr = ev_word(io, rc);
+                rts[k] = r >= 0 ? ev_time(io, mr, rc) : (io.cts ? io.cts[base + k] : g.t[k]);
+                rfl[k] = ev_flags(mr);
             }
 #pragma unroll
             for (int k = 0; k < FG; k++) {
@@ -2165,26 +2075,14 @@ using HeadIter = rocprim::transform_iterator<rocprim::counting_iterator<uint32_t
 using HeadScanCfg = SF_HEAD_SCAN_CFG;
 using PcScanCfg = SF_PC_SCAN_CFG;
 
-hipError_t query_temp_bytes(uint32_t max_n, uint32_t key_bits, size_t* sort_bytes, size_t* scan_bytes,
-                            size_t* pscan_bytes) {
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, *sort_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                             (uint32_t*)nullptr, (uint32_t*)nullptr, max_n, 0u, key_bits);
-    if (e != hipSuccess) return e;
-    size_t packed_bytes = 0;
-    e = rocprim::radix_sort_pairs(nullptr, packed_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                  (PackedEv*)nullptr, (PackedEv*)nullptr, max_n, 0u, key_bits);
-    if (e != hipSuccess) return e;
-    if (packed_bytes > *sort_bytes) *sort_bytes = packed_bytes;
-    e = rocprim::radix_sort_pairs(nullptr, packed_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                  (PackedEvO*)nullptr, (PackedEvO*)nullptr, max_n, 0u, key_bits);
-    if (e != hipSuccess) return e;
-    if (packed_bytes > *sort_bytes) *sort_bytes = packed_bytes;
-    if (rs_scratch_bytes() > *sort_bytes) *sort_bytes = rs_scratch_bytes();
+hipError_t query_temp_bytes(uint32_t max_n, size_t* sort_bytes, size_t* scan_bytes, size_t* pscan_bytes) {
+    *sort_bytes = rs_scratch_bytes();
+    hipError_t e;
     HeadIter hit(rocprim::counting_iterator<uint32_t>(0), HeadFlag{nullptr});
     e = rocprim::inclusive_scan<HeadScanCfg>(nullptr, *scan_bytes, hit, (uint32_t*)nullptr, (size_t)max_n,
                                 rocprim::plus<uint32_t>());
     if (e != hipSuccess) return e;
-    PcIter it(rocprim::counting_iterator<uint32_t>(0), EntryCount{nullptr, nullptr});
+    PcIter it(rocprim::counting_iterator<uint32_t>(0), EntryCount{SortedEv{}});
     return rocprim::inclusive_scan<PcScanCfg>(nullptr, *pscan_bytes, it, (int64_t*)nullptr, (size_t)max_n,
                                    rocprim::plus<int64_t>());
 }
@@ -2227,21 +2125,17 @@ static void launch_classify(const DevState& st, Work& w, const DevBatch& b, hipS
     launch_fill(f, s);
     const uint32_t max_seg = n < st.R ? n : st.R;
     if (timing) hipEventRecord(ev[10], s);
-    hipLaunchKernelGGL(k_classify, dim3(blocks(max_seg, 1024)), dim3(1024), 0, s, st, w, w.s_ts);
+    hipLaunchKernelGGL(k_classify, dim3(blocks(max_seg, 1024)), dim3(1024), 0, s, st, w, sorted_ev(w, b));
     HeavyCtx hc = heavy_ctx(w);
     StreamCtx sc{w.stream_list, w.counters + 5, w.seg_cap, nullptr, w.counters + 7};
     hipLaunchKernelGGL(k_fill_tiles, dim3(2), dim3(1024), 0, s, hc, sc, w.fill_tiles, w.fill_tile_cap, w.fill_ntiles);
     if (timing) hipEventRecord(ev[2], s);
 }
 
-static bool sort_uses_rocprim() {
-    static const bool v = [] { const char* x = getenv("SF_SORT_ROCPRIM"); return x && x[0] == '1'; }();
-    return v;
-}
 // k_segs_red / _tscan / _out or, SF_SEGS_LB=0, the rocprim head scan + k_segs + the rocprim acquireCount scan (A/B)
 static bool segs_one_pass() {
     static const bool v = [] { const char* x = getenv("SF_SEGS_LB"); return !(x && x[0] == '0'); }();
-    return v && !sort_uses_rocprim();
+    return v;
 }
 
 hipError_t launch_sort(const DevState& st, Work& w, const DevBatch& b, uint32_t shard_count, uint32_t shard_index,
@@ -2252,31 +2146,16 @@ hipError_t launch_sort(const DevState& st, Work& w, const DevBatch& b, uint32_t 
     if (timing) hipEventRecord(ev[0], s);
     hipError_t e;
     const bool org = b.origin != nullptr;                       // the origin rides in a 12-B payload
-    // the hand-written chunked LSD sort (sf_rsort.h); SF_SORT_ROCPRIM=1: k_keys_packed + rocprim onesweep (A/B)
-    const bool use_rocprim = sort_uses_rocprim();
-    if (!use_rocprim) {
-        // middle passes in (keys_in, pv_in) and (head_scan, pv_out); the last pass writes keys_out and the sorted SoA
-        const RsBatchSrc src{b, shard_count, shard_index, st.R, st.err, st.last_ts, st.xmap};
-        if (org) {
-            const RsSinkFinal<PackedEvO> fin{b, w.keys_out, w.perm, w.s_ts, w.s_cnt, w.s_flags, w.s_origin,
-                                             w.s_nargs, w.s_atag, w.s_abits};
-            e = rs_sort(src, n, key_bits, w.keys_in, (PackedEvO*)w.pv_in, w.head_scan, (PackedEvO*)w.pv_out, fin,
-                        w.sort_tmp, s);
-        } else {
-            const RsSinkFinal<PackedEv> fin{b, w.keys_out, w.perm, w.s_ts, w.s_cnt, w.s_flags, nullptr,
-                                            w.s_nargs, w.s_atag, w.s_abits};
-            e = rs_sort(src, n, key_bits, w.keys_in, w.pv_in, w.head_scan, w.pv_out, fin, w.sort_tmp, s);
-        }
-    } else if (org) {
-        hipLaunchKernelGGL(k_keys_packed<true>, dim3(blocks(n, T)), dim3(T), 0, s, b, w.keys_in, (void*)w.pv_in,
-                           shard_count, shard_index, st.R, st.err, st.last_ts, st.xmap);
-        e = rocprim::radix_sort_pairs(w.sort_tmp, w.sort_tmp_bytes, w.keys_in, w.keys_out, (PackedEvO*)w.pv_in,
-                                      (PackedEvO*)w.pv_out, n, 0u, key_bits, s);
+    // the chunked LSD sort (sf_rsort.h): middle passes in (keys_in, pv_in) and
+    // (head_scan, pv_out); the last pass writes keys_out, perm, s_meta and the arguments
+    const RsBatchSrc src{b, shard_count, shard_index, st.R, st.err, st.last_ts, st.xmap};
+    if (org) {
+        const RsSinkFinal<PackedEvO> fin{b, w.keys_out, w.perm, w.s_meta, w.s_origin, w.s_nargs, w.s_atag, w.s_abits};
+        e = rs_sort(src, n, key_bits, w.keys_in, (PackedEvO*)w.pv_in, w.head_scan, (PackedEvO*)w.pv_out, fin,
+                    w.sort_tmp, s);
     } else {
-        hipLaunchKernelGGL(k_keys_packed<false>, dim3(blocks(n, T)), dim3(T), 0, s, b, w.keys_in, (void*)w.pv_in,
-                           shard_count, shard_index, st.R, st.err, st.last_ts, st.xmap);
-        e = rocprim::radix_sort_pairs(w.sort_tmp, w.sort_tmp_bytes, w.keys_in, w.keys_out, w.pv_in, w.pv_out, n, 0u,
-                                      key_bits, s);
+        const RsSinkFinal<PackedEv> fin{b, w.keys_out, w.perm, w.s_meta, nullptr, w.s_nargs, w.s_atag, w.s_abits};
+        e = rs_sort(src, n, key_bits, w.keys_in, w.pv_in, w.head_scan, w.pv_out, fin, w.sort_tmp, s);
     }
     if (e != hipSuccess) return e;
     if (!segs_one_pass()) {
@@ -2287,24 +2166,15 @@ hipError_t launch_sort(const DevState& st, Work& w, const DevBatch& b, uint32_t 
     }
     hipMemsetAsync(w.segflag, 0, (size_t)(n < st.R ? n : st.R) * 4, s);
     if (timing) hipEventRecord(ev[1], s);
-    if (!use_rocprim && !segs_one_pass()) {
-        hipLaunchKernelGGL(k_segs, dim3(blocks(n, T)), dim3(T), 0, s, b, w.s_cnt, w.s_flags, w.s_atag, w.keys_out,
+    if (!segs_one_pass()) {
+        hipLaunchKernelGGL(k_segs, dim3(blocks(n, T)), dim3(T), 0, s, b, sorted_ev(w, b), w.s_atag, w.keys_out,
                            w.head_scan, w.seg_start, w.seg_res, w.n_seg, w.segflag, st.last_ts, st.err,
                            st.n_prule != 0, st.prio_seen);
-    } else if (!use_rocprim) {
+    } else {
         // segment table, head scan and (window rules loaded) the acquireCount prefix: reduce, scan, rescan
         if (st.n_window_rules) launch_segs3<true>(st, w, b, s);
         else launch_segs3<false>(st, w, b, s);
-    } else if (org)
-        hipLaunchKernelGGL(k_unpack<true>, dim3(blocks(n, T)), dim3(T), 0, s, b, (const void*)w.pv_out, w.keys_out,
-                           w.perm, w.s_ts, w.s_cnt, w.s_flags, w.s_nargs, w.s_atag, w.s_abits, w.head_scan,
-                           w.seg_start, w.seg_res, w.n_seg, w.segflag, st.last_ts, st.err, st.n_prule != 0, w.s_origin,
-                           st.prio_seen);
-    else
-        hipLaunchKernelGGL(k_unpack<false>, dim3(blocks(n, T)), dim3(T), 0, s, b, (const void*)w.pv_out, w.keys_out,
-                           w.perm, w.s_ts, w.s_cnt, w.s_flags, w.s_nargs, w.s_atag, w.s_abits, w.head_scan,
-                           w.seg_start, w.seg_res, w.n_seg, w.segflag, st.last_ts, st.err, st.n_prule != 0,
-                           (uint32_t*)nullptr, st.prio_seen);
+    }
     if (classify) launch_classify(st, w, b, s, ev, timing);
     return hipGetLastError();
 }
@@ -2483,13 +2353,14 @@ static void launch_thr_prep(Work& w, const DevBatch& b, hipStream_t s) {
     const uint32_t tile_ub = n / FILL_TILE + n / (w.heavy_min + 1) + 2;
     const uint2* tiles1 = w.fill_tiles + w.fill_tile_cap;
     const int64_t* seref = b.eref ? w.s_eref : nullptr;
+    const SortedEv ev = sorted_ev(w, b);
     const dim3 tgrid(std::min<uint32_t>(1024u, tile_ub));
-    hipLaunchKernelGGL(k_thr_heads, tgrid, dim3(256), 0, s, w.s_flags, w.s_cnt, hc, tiles1, w.fill_ntiles,
+    hipLaunchKernelGGL(k_thr_heads, tgrid, dim3(256), 0, s, ev, hc, tiles1, w.fill_ntiles,
                        w.tile_rc, w.segflag);
     // THREAD run mode tables (sf_stream.h thr_runs_segment)
     hipLaunchKernelGGL(k_thr_rscan, dim3(1), dim3(1024), 0, s, w.tile_rc, w.fill_ntiles);
-    hipLaunchKernelGGL(k_thr_rid, tgrid, dim3(256), 0, s, w.s_flags, hc, tiles1, w.fill_ntiles, w.tile_rc);
-    hipLaunchKernelGGL(k_thr_rec, tgrid, dim3(256), 0, s, w.s_flags, w.s_cnt, seref, hc, tiles1, w.fill_ntiles,
+    hipLaunchKernelGGL(k_thr_rid, tgrid, dim3(256), 0, s, ev, hc, tiles1, w.fill_ntiles, w.tile_rc);
+    hipLaunchKernelGGL(k_thr_rec, tgrid, dim3(256), 0, s, ev, seref, hc, tiles1, w.fill_ntiles,
                        w.segflag);
 }
 
@@ -2523,7 +2394,8 @@ hipError_t launch_decide(const DevState& st, Work& w, const DevBatch& b, const D
     if (n == 0) return hipSuccess;
     if (classify) launch_classify(st, w, b, s, ev, timing);
     SegIO io;
-    io.ts = w.s_ts; io.cnt = w.s_cnt; io.flags = w.s_flags;
+    io.ts = nullptr; io.cnt = nullptr; io.flags = nullptr;     // (host build only)
+    io.ev = sorted_ev(w, b);
     io.eref = b.eref ? w.s_eref : nullptr; io.cts = b.eref ? w.s_cts : nullptr;
     io.arg_slots = b.arg_slots; io.nargs = (b.arg_slots && b.nargs) ? w.s_nargs : nullptr;
     io.atag = w.s_atag; io.abits = w.s_abits; io.n = n;
@@ -2550,7 +2422,7 @@ hipError_t launch_decide(const DevState& st, Work& w, const DevBatch& b, const D
         launch_fill(f, s);
     }
     if (b.eref)
-        hipLaunchKernelGGL(k_gather_exit, dim3(blocks(n, 256)), dim3(256), 0, s, b, w.perm, w.s_flags,
+        hipLaunchKernelGGL(k_gather_exit, dim3(blocks(n, 256)), dim3(256), 0, s, b, w.perm, w.s_meta,
                            w.head_scan, w.seg_start, w.s_eref, w.s_cts, w.exit_of, st.err);
     hipEventRecord(ev[5], s);                      // fork
     // (the THREAD / RateLimiter class exists only with such rules loaded)
@@ -2583,7 +2455,7 @@ hipError_t launch_decide(const DevState& st, Work& w, const DevBatch& b, const D
         // acquireCount prefix of the entries (QPS / WarmUp window budgets, k_heavy_decide
         // only; the hand-written sort path writes it in k_segs_out): state-independent, but
         // here on stream B rather than in the sort phase, the longer of the two pipelined phases
-        PcIter it(rocprim::counting_iterator<uint32_t>(0), EntryCount{w.s_cnt, w.s_flags});
+        PcIter it(rocprim::counting_iterator<uint32_t>(0), EntryCount{sorted_ev(w, b)});
         const hipError_t e = rocprim::inclusive_scan<PcScanCfg>(w.pscan_tmp, w.pscan_tmp_bytes, it, w.pcg,
                                                                 (size_t)n, rocprim::plus<int64_t>(), s2);
         if (e != hipSuccess) return e;

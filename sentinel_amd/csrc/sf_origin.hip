@@ -527,7 +527,7 @@ __global__ void __launch_bounds__(OX_T) k_ox_index(DevState st, DevBatch b, OxId
 // ------------------------------------------------------------------ decide phase
 struct OxRun {
     const uint32_t* seg_start; const uint8_t* seg_mode;
-    const int64_t* ts; const int32_t* cnt; const uint8_t* flags; const int64_t* eref; const int64_t* cts;
+    SortedEv ev; const int64_t* eref; const int64_t* cts;
     const uint8_t* v_status; const uint32_t* s_oslot;
     const uint32_t* hmap; const uint32_t* hslot; OxAcc* acc; int64_t* thr;
     const uint32_t* bflags; const uint2* bseg; const uint4* pairs; const uint32_t* plist;
@@ -587,13 +587,14 @@ struct OxNode {
 
 // StatisticSlot's update of the origin node for sorted event j (verdict known)
 __device__ __forceinline__ void ox_apply_event(OxNode& on, const OxRun& r, uint32_t j) {
-    const uint8_t v = r.v_status[j], fl = r.flags[j];
-    const int64_t t = r.ts[j];
-    const int32_t c = r.cnt[j];
+    const uint32_t m = r.ev.meta[j];
+    const uint8_t v = r.v_status[j], fl = ev_flags(m);
+    const int64_t t = ev_time(r.ev, m, j);
+    const int32_t c = ev_count(r.ev, m, j);
     if (fl & SF_EV_EXIT) {                                   // StatisticSlot.exit :139-165 (recordCompleteFor)
         if (v != SF_V_EXIT) return;                          // its entry was blocked: nothing is recorded
         const int64_t ref = r.eref ? r.eref[j] : -1;
-        const int64_t cts = ref >= 0 ? r.ts[ref] : (r.cts ? r.cts[j] : t);
+        const int64_t cts = ref >= 0 ? ev_time(r.ev, (uint32_t)ref) : (r.cts ? r.cts[j] : t);
         const int64_t rt = t - cts;
         on.add(t, [&](Bucket& b) {                           // StatisticNode.addRtAndSuccess, MetricBucket.addRT
             b.succ = wadd(b.succ, c); b.rt = wadd(b.rt, rt); if (rt < b.min_rt) b.min_rt = rt;
@@ -613,6 +614,7 @@ __device__ __forceinline__ void ox_apply_event(OxNode& on, const OxRun& r, uint3
 // and few registers: many wavefronts keep the bucket loads of many pairs in
 // flight.
 __global__ void __launch_bounds__(256) k_ox_lapply(DevState st, OxRun r, uint32_t npairs) {
+    ev_open(r.ev);
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= npairs) return;
     const uint4 pr = r.pairs[t];
@@ -645,6 +647,7 @@ __device__ __forceinline__ void ox_add_row(unsigned long long* v, const unsigned
 // row's pair id (hmap) and one set of global atomics.  Rows: the second
 // window, the minute window, the thread delta (row W).
 __global__ void __launch_bounds__(OX_T) k_ox_hacc(DevState st, OxRun r) {
+    ev_open(r.ev);
     __shared__ OxRow rows[OX_HCAP];
     __shared__ uint32_t sst[OX_TILE + 1];        // starts of the segments overlapping the block, then their end
     const uint32_t tid = threadIdx.x;
@@ -668,16 +671,17 @@ __global__ void __launch_bounds__(OX_T) k_ox_hacc(DevState st, OxRun r) {
         if (sst[a_ + 1] - sst[a_] <= OX_LIGHT || r.seg_mode[bs.x + a_] == SM_XFLOW) continue;
         const uint32_t a = r.s_oslot[j];
         if (a == XNONE) continue;
-        const uint8_t v = r.v_status[j], fl = r.flags[j];
-        const int64_t t = r.ts[j];
-        const int32_t c = r.cnt[j];
+        const uint32_t mw = r.ev.meta[j];
+        const uint8_t v = r.v_status[j], fl = ev_flags(mw);
+        const int64_t t = ev_time(r.ev, mw, j);
+        const int32_t c = ev_count(r.ev, mw, j);
         unsigned long long d[7] = {0, 0, 0, 0, 0, 0, 0};
         int64_t dthr = 0;
         bool touch = true;
         if (fl & SF_EV_EXIT) {
             if (v != SF_V_EXIT) continue;
             const int64_t ref = r.eref ? r.eref[j] : -1;
-            const int64_t cts = ref >= 0 ? r.ts[ref] : (r.cts ? r.cts[j] : t);
+            const int64_t cts = ref >= 0 ? ev_time(r.ev, (uint32_t)ref) : (r.cts ? r.cts[j] : t);
             const int64_t rt = t - cts;
             d[2] = (unsigned long long)(int64_t)c; d[3] = (unsigned long long)rt;
             if (fl & SF_EV_ERROR) d[4] = (unsigned long long)(int64_t)c;
@@ -807,7 +811,7 @@ hipError_t launch_ox_apply(const DevState& st, Work& w, const DevBatch& b, uint3
     if (!b.n) return hipSuccess;
     OxRun r{};
     r.seg_start = w.seg_start; r.seg_mode = w.seg_mode;
-    r.ts = w.s_ts; r.cnt = w.s_cnt; r.flags = w.s_flags;
+    r.ev = SortedEv{w.s_meta, w.perm, b.ts, b.cnt, 0};
     r.eref = b.eref ? w.s_eref : nullptr; r.cts = b.eref ? w.s_cts : nullptr;
     r.v_status = w.v_status; r.s_oslot = w.s_oslot;
     r.hmap = w.ox_hmap; r.hslot = w.ox_hslot; r.acc = (OxAcc*)w.ox_acc; r.thr = w.ox_thr;

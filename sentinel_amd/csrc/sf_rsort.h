@@ -19,13 +19,13 @@
 //   Ranks follow (tile, wave, row, lane) = input order: the sort is stable.
 //
 // Pass 0 reads the caller's batch itself (key = shard-local resource id, or
-// its xflow group key; the 8-B / 12-B payload of k_keys_packed; the checks of
+// its xflow group key; the 8-B / 12-B payload; the checks of
 // the resource's shard and of the clock order), so no key array is written
 // before the first pass.  A chunk's tile stream is written by one workgroup on
 // one CU, so the partial lines at a bin run's ends are completed by the same
 // workgroup's next tile while still in its XCD's L2.
 #pragma once
-#include "sf_internal.h"
+#include "sf_decide.h"
 
 namespace sf {
 
@@ -39,23 +39,12 @@ constexpr int RS_DB = SF_RS_DB, RS_NB = 1 << RS_DB, RS_W = SF_RS_W;
 constexpr int RS_T = RS_W * 64;
 constexpr uint32_t RS_MAX_CHUNKS = 1024;
 
-// the event's payload (sf_internal.h PackedEv): index, time offset from the
-// batch's first event, flags (the planner's forced SystemBlockException and
-// AuthoritySlot blocks folded in), acquireCount when it fits in 8 bits
+// the event's word (ev_pack, sf_decide.h): the planner's forced
+// SystemBlockException and AuthoritySlot blocks folded into the flags
 __device__ __forceinline__ uint32_t rs_meta(const DevBatch& b, uint32_t i, int64_t ts, int64_t ts0) {
-    const int64_t d = ts - ts0;
-    const uint32_t dts = (d >= 0 && d < (int64_t)PV_DTS_FAR) ? (uint32_t)d : PV_DTS_FAR;
     const uint8_t f = b.flags[i];
-    uint32_t fl = f & 0x0Fu;
-    if ((f & (SF_EV_BLOCKED | SF_EV_EXIT)) == SF_EV_BLOCKED)     // blocked by AuthoritySlot (before SystemSlot)
-        fl |= EVF_SYSBLK | ((uint32_t)SYSR_OTHER << EVF_SYSREASON_SHIFT);
-    else if (b.sys && (f & SF_EV_IN) && !(f & SF_EV_EXIT)) {     // SystemBlockException forced by the planner
-        const uint8_t sr = b.sys[i];
-        if (sr < SYS_INERT) fl |= EVF_SYSBLK | ((uint32_t)sr << EVF_SYSREASON_SHIFT);   // (SYS_INERT / SYS_NONE: none)
-    }
-    const int32_t c = b.cnt[i];
-    const uint32_t c8 = (c >= 1 && c <= 255) ? (uint32_t)c : 0u;
-    return dts | (fl << 16) | (c8 << 24);
+    const uint8_t sr = (b.sys && (f & SF_EV_IN) && !(f & SF_EV_EXIT)) ? b.sys[i] : SYS_NONE;
+    return ev_pack(ts, ts0, f, sr, b.cnt[i]);
 }
 
 __device__ __forceinline__ void rs_put_origin(uint32_t*, uint32_t, const PackedEv&) {}
@@ -236,22 +225,20 @@ struct RsSinkKV {
     uint32_t* k; V* v;
     __device__ __forceinline__ void put(uint32_t dst, uint32_t key, const V& val) const { k[dst] = key; rs_cp(v[dst], val); }
 };
-// the last pass: the sorted SoA the decide phase reads (k_unpack's per-event
-// part): key, submission index, time, acquireCount, flags, origin, and the
-// ParamFlow arguments gathered from the batch
+// the last pass: what the decide phase reads in sorted order: key, submission
+// index, the event's word as it is (time, flags and acquireCount are decoded
+// by the readers, sf_decide.h ev_*), origin, and the ParamFlow arguments
+// gathered from the batch
 template <class V>
 struct RsSinkFinal {
     DevBatch b;
-    uint32_t* keys; uint32_t* perm; int64_t* s_ts; int32_t* s_cnt; uint8_t* s_flags;
+    uint32_t* keys; uint32_t* perm; uint32_t* s_meta;
     uint32_t* s_origin; uint8_t* s_nargs; uint8_t* s_atag; uint64_t* s_abits;
     __device__ __forceinline__ void put(uint32_t j, uint32_t key, const V& val) const {
         keys[j] = key;
         const uint32_t i = val.idx;
-        const uint32_t dts = val.meta & 0xffffu, c8 = val.meta >> 24;
         perm[j] = i;
-        s_ts[j] = dts != PV_DTS_FAR ? b.ts[0] + (int64_t)dts : b.ts[i];
-        s_cnt[j] = c8 ? (int32_t)c8 : b.cnt[i];
-        s_flags[j] = (uint8_t)(val.meta >> 16);
+        s_meta[j] = val.meta;
         rs_put_origin(s_origin, j, val);
         if (b.arg_slots) {
             if (b.nargs) s_nargs[j] = b.nargs[i];

@@ -622,9 +622,10 @@ __device__ __forceinline__ void rl_load(RlRegs& r, const SegIO& io, uint32_t q0,
 #pragma unroll
     for (int i = 0; i < HS_PL; i++) {
         const uint32_t j = min(q0 + (uint32_t)(i * HS_T) + threadIdx.x, hi - 1);
-        r.ts[i] = io.ts[j];
-        r.c[i] = io.cnt[j];
-        f[i] = io.flags[j];
+        const uint32_t m = ev_word(io, j);
+        r.ts[i] = ev_time(io, m, j);
+        r.c[i] = ev_count(io, m, j);
+        f[i] = ev_flags(m);
     }
 #pragma unroll
     for (int i = 0; i < HS_PL; i++) {
@@ -791,7 +792,7 @@ __device__ void thr_runs_segment(const DevState& st, const SegIO& io, const Heav
     const int lane = (int)(threadIdx.x & 63);
     const uint32_t rb = hc.seg_rb[s], nr = hc.seg_re[s] - rb;
     // runs alternate kinds: run k holds entries iff (k & 1) == e0
-    const uint32_t e0 = is_checked_entry(io.flags[lo]) ? 0u : 1u;
+    const uint32_t e0 = is_checked_entry(ev_flags(io, lo)) ? 0u : 1u;
     int64_t T = uniform64(st.threads[res]);
     unsigned long long* pbits = hc.passbits;
     const uint2* rrec = hc.rrec;
@@ -1032,6 +1033,7 @@ __device__ void stream_segment(const DevState& st, const SegIO& io, const HeavyC
 // them one segment at a time.  Every workgroup leaves when the queue is
 // exhausted.
 __global__ void __launch_bounds__(HS_T) k_heavy_stream(DevState st, SegIO io, HeavyCtx hc, StreamCtx sc) {
+    ev_open(io.ev);
     __shared__ unsigned long long smem[HS_SMEM_WORDS];
     __shared__ uint32_t slot;
     while (true) {

@@ -15,7 +15,7 @@
 //
 // Resources with such rules, and the resources their RELATE rules read, are
 // grouped (connected by RELATE references) and each group's events are sorted
-// into ONE segment (k_keys_packed maps every member to the group key), so one
+// into ONE segment (the sort's first pass maps every member to the group key), so one
 // lane replays the group in submission order — a RELATE check reads the other
 // resource's ClusterNode exactly as the events before it left it.  All node
 // state of the walk lives in HBM (held in NodeWins while consecutive events
@@ -136,9 +136,10 @@ SF_HD void xg_event(const DevState& st, const SegIO& io, const ParamTable& pt, u
     const uint32_t l = gres / io.shard_count;
     const uint32_t origin = io.ev_origin ? io.ev_origin[i] : SF_ORIGIN_NONE;
     const uint32_t ctx = io.ev_ctx ? io.ev_ctx[i] : 0u;
-    const int64_t now = io.ts[j];
-    const int32_t c = io.cnt[j];
-    const uint8_t fl = io.flags[j];
+    const uint32_t mw = ev_word(io, j);
+    const int64_t now = ev_time(io, mw, j);
+    const int32_t c = ev_count(io, mw, j);
+    const uint8_t fl = ev_flags(mw);
     const uint32_t na = io.arg_slots ? (io.nargs ? io.nargs[j] : io.arg_slots) : 0;
     const uint32_t r0 = st.rule_off[l], r1 = st.rule_off[l + 1];
     // the origin node of every entry with an origin (ClusterBuilderSlot.java:107-110:
@@ -181,13 +182,13 @@ SF_HD void xg_event(const DevState& st, const SegIO& io, const ParamTable& pt, u
         int64_t ref = io.eref ? io.eref[j] : -1;
         bool blocked; int64_t create_ts;
         if (ref >= 0) {
-            if (ref < (int64_t)lo || ref >= (int64_t)j || (io.flags[ref] & SF_EV_EXIT) ||
+            if (ref < (int64_t)lo || ref >= (int64_t)j || (ev_flags(io, (uint32_t)ref) & SF_EV_EXIT) ||
                 io.ev_res[io.perm[ref]] != gres) {
                 *st.err = SF_ERR_INVALID;
                 ref = j;
             }
             blocked = ref == (int64_t)j ? true : v_blocked(io.v_status[ref]);
-            create_ts = io.ts[ref];
+            create_ts = ev_time(io, (uint32_t)ref);
         } else {
             blocked = ref == EREF_DEAD; create_ts = io.cts ? io.cts[j] : now;
         }
