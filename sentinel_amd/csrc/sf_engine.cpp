@@ -1,9 +1,12 @@
 // sf_engine.cpp — host runtime behind the C-ABI (include/sentinel_flow.h).
 //
-// Owns one GPU's shard of resource state in HBM, the rule tables, the batch
-// working buffers and one HIP stream.  sf_submit is serialised by a mutex
-// (the Java shim batches from many threads into one flusher).
-// There is no CPU fallback: without a usable gfx950 device sf_create fails.
+// Owns one GPU's shard of resource state in HBM, the rule tables and the
+// batch pipeline: SF_SLOTS batches in flight (struct Slot) over the sort
+// stream, the decide streams (`stream` and its fork / join streams 2-4), the
+// ENTRY_NODE side stream of asynchronous batches and the packed path's two
+// copy streams.  The entry points are serialised by a mutex (the Java shim
+// batches from many threads into one flusher).  There is no
+// CPU fallback: without a usable gfx950 device sf_create fails.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,6 +49,42 @@ struct StageBuf {
     const uint8_t* st_src = nullptr; uint32_t st_n = 0;    // verdicts [0, st_n) of st_src already staged
 };
 
+// compact batches (sf_submit_packed): the device copy of the packed input of
+// one slot's batch, its SoA expansion and the verdicts copied back
+struct PkStage {
+    char* buf = nullptr; size_t bytes = 0;
+    hipEvent_t h2d = nullptr, d2h = nullptr;
+    hipEvent_t consumed = nullptr;     // the packed inputs expanded (the next H2D into them may start)
+    bool d2h_pending = false, consumed_pending = false;
+    const uint8_t* out_status = nullptr;   // host verdicts of the async batch in flight (sf_sync_packed)
+    int32_t* err_host = nullptr;           // its error flag, copied back with its verdicts (pinned)
+    // sf_sparse_verdicts of that batch: the caller's struct, the list lengths
+    // (pinned, copied back with the status bytes), the device lists
+    bool sparse = false;
+    sf_sparse_verdicts sp{};
+    uint32_t* sp_counts = nullptr;
+    const unsigned long long* sp_wl = nullptr; const unsigned long long* sp_rl = nullptr;
+};
+
+// Everything one batch in flight owns.  Batch k sorts into slot k % SF_SLOTS
+// while batch k-1 is decided; a synchronous batch does not advance the slot.
+// The count stays 2: the wait in take_slot ("two submits ago") and the packed
+// stage's reuse rules (submit_packed) are argued for two slots, and whether
+// the pipeline is correct with three is not established.
+constexpr int SF_SLOTS = 2;
+struct Slot {
+    Work w{};                       // the sorted-order buffers (allocated on first use: ready)
+    bool ready = false;
+    bool used = false;              // a batch has been enqueued into the slot (its events are recorded)
+    bool timed = false;             // that batch ran with timing on and is not yet in stats
+    hipEvent_t sorted = nullptr;    // its sort phase is enqueued (the decide streams wait for it)
+    hipEvent_t done = nullptr;      // its verdicts are scattered: the Work set is free
+    hipEvent_t end = nullptr;       // done and its ENTRY_NODE update (which reads the caller's batch)
+    hipEvent_t core = nullptr;      // its verdicts are written (the packed D2H copy waits for it)
+    hipEvent_t evs[SF_NUM_EVENTS]{};   // fork / join and timing events of its batch
+    PkStage pk;
+};
+
 struct sf_engine {
     sf_config cfg{};
     hipStream_t stream = nullptr, stream2 = nullptr, stream3 = nullptr, stream4 = nullptr;   // 4: the wave walk
@@ -62,14 +101,9 @@ struct sf_engine {
     bool serial = false;            // diagnostics (SF_SERIAL_STREAMS=1): every kernel on one stream
     uint32_t R = 0, key_bits = 1;
     DevState st{};
-    Work w[2]{};                    // two Work sets: batch k sorts into w[k % 2] while k-1 is decided
-    bool w_ready[2] = {false, false};
-    int cur = 0, last = 0;          // Work set of the next / last submitted batch
-    unsigned pending = 0;           // Work sets with an asynchronous batch not yet checked by sf_sync
-    bool used[2] = {false, false};
-    hipEvent_t ev_sorted[2]{}, ev_done[2]{};
-    hipEvent_t ev_end[2]{};                          // ev_done and the batch's ENTRY_NODE update (reads the batch)
-    hipEvent_t ev_core[2]{};                         // the verdicts of the slot's batch are written
+    Slot slot[SF_SLOTS];
+    int cur = 0, last = 0;          // slot of the next / last submitted batch
+    unsigned pending = 0;           // slots (bit k) with an asynchronous batch not yet checked by sf_sync
     SysRule sys{};                  // SystemRuleManager statics; sys.check: batches go through the planner
     SysPlanDev* sys_plan = nullptr; SysExitQ* sys_pa = nullptr; SysEntQ* sys_pb = nullptr;
     uint8_t* sys_ibuf = nullptr;                  // the planner's inert flags (sys_plan)
@@ -85,8 +119,6 @@ struct sf_engine {
     void* stage_in = nullptr; size_t stage_in_bytes = 0;
     void* stage_out = nullptr; size_t stage_out_bytes = 0;
     StageBuf plan_sb, en_sb;                       // sf_system_plan / sf_entry_node_add inputs
-    hipEvent_t evs[2][SF_NUM_EVENTS]{};   // per Work set: fork/join and timing events of its batch
-    bool timed[2] = {false, false};       // that batch ran with timing on and is not yet in stats
     bool timing = false;
     sf_stats stats{};
     std::vector<void*> user_allocs;
@@ -146,23 +178,7 @@ struct sf_engine {
     std::vector<AuxChunk> ax_host;
     AuxChunk* ax_dir = nullptr;
     uint64_t aux_grows = 0;
-    // compact batches (sf_submit_packed): per Work set, the device copy of the
-    // packed input, its SoA expansion and the verdicts copied back; copy
-    // streams so that H2D(k+1), decide(k) and D2H(k-1) overlap
-    struct PkStage {
-        char* buf = nullptr; size_t bytes = 0;
-        hipEvent_t h2d = nullptr, d2h = nullptr;
-        hipEvent_t consumed = nullptr;     // the packed inputs expanded (the next H2D into them may start)
-        bool d2h_pending = false, consumed_pending = false;
-        const uint8_t* out_status = nullptr;   // host verdicts of the async batch in flight (sf_sync_packed)
-        int32_t* err_host = nullptr;           // its error flag, copied back with its verdicts (pinned)
-        // sf_sparse_verdicts of that batch: the caller's struct, the list lengths
-        // (pinned, copied back with the status bytes), the device lists
-        bool sparse = false;
-        sf_sparse_verdicts sp{};
-        uint32_t* sp_counts = nullptr;
-        const unsigned long long* sp_wl = nullptr; const unsigned long long* sp_rl = nullptr;
-    } pk[2];
+    // copy streams of compact batches (PkStage): H2D(k+1), decide(k) and D2H(k-1) overlap
     hipStream_t h2d = nullptr, d2h = nullptr;
     int32_t* rh_err = nullptr;            // rehash_table's overflow flag
 };
@@ -201,14 +217,14 @@ static int dalloc(void** p, size_t bytes) {
     } while (0)
 
 static void free_work(Work& w) {
-    void* ptrs[] = {w.pv_in, w.pv_out, w.wide, w.err, w.keys_in, w.keys_out, w.perm, w.head, w.head_scan,
+    void* ptrs[] = {w.pv_in, w.pv_out, w.err, w.keys_in, w.keys_out, w.perm, w.head, w.head_scan,
                     w.seg_start, w.seg_res, w.n_seg, w.s_meta, w.s_eref,
                     w.s_cts, w.s_nargs, w.s_atag, w.s_abits, w.v_status, w.v_wait,
                     w.v_rule, w.sort_tmp, w.scan_tmp,
                     w.segflag, w.seg_mode, w.light_list, w.lcounts, w.heavy_list, w.counters, w.pcg, w.segs_lb,
                     w.pscan_tmp, w.fill_tiles, w.fill_ntiles, w.acc_hw,
                     w.acc_sec, w.acc_hw_base, w.acc_sec_base, w.seg_hw0, w.seg_sec0,
-                    w.seg_nhw, w.seg_nsec, w.hticks, w.passbits, w.stream_list, w.sticks,
+                    w.seg_nhw, w.seg_nsec, w.hticks, w.passbits, w.stream_list, w.xw_list, w.sticks,
                     w.exit_of, w.lxfar, w.thr_rec, w.vs_cursor, w.tile_rc, w.seg_rb, w.seg_re,
                     w.s_origin, w.s_oslot, w.ox_cnt, w.ox_bflags, w.ox_hmap, w.ox_hslot, w.ox_thr, w.ox_acc,
                     w.ox_bseg, w.ox_pairs, w.ox_plist};
@@ -216,61 +232,53 @@ static void free_work(Work& w) {
     w = Work{};
 }
 
+// the events of a slot (the packed stage's are created with its copy streams, submit_packed)
+static int slot_create(Slot& sl) {
+    for (auto& x : sl.evs) HIP_TRY(hipEventCreate(&x));
+    for (hipEvent_t* x : {&sl.sorted, &sl.done, &sl.end, &sl.core})
+        HIP_TRY(hipEventCreateWithFlags(x, hipEventDisableTiming));
+    return SF_OK;
+}
+
+static void slot_destroy(Slot& sl) {
+    free_work(sl.w);
+    PkStage& p = sl.pk;
+    if (p.buf) hipFree(p.buf);
+    if (p.err_host) hipHostFree(p.err_host);
+    if (p.sp_counts) hipHostFree(p.sp_counts);
+    for (hipEvent_t x : {p.h2d, p.d2h, p.consumed, sl.sorted, sl.done, sl.end, sl.core}) if (x) hipEventDestroy(x);
+    for (hipEvent_t x : sl.evs) if (x) hipEventDestroy(x);
+}
+
 void sf_destroy(sf_engine* e) {
     if (!e) return;
     if (e->sstream) hipStreamSynchronize(e->sstream);
     if (e->stream) hipStreamSynchronize(e->stream);
-    for (Work& w : e->w) free_work(w);
     void* ptrs[] = {e->st.second, e->st.borrow, e->st.minute, e->st.threads, (void*)e->st.rule_off,
                     (void*)e->st.rules, e->st.rstate, (void*)e->st.prule_off, e->st.prules, (void*)e->st.items,
                     e->st.pm_init, e->st.ptab, e->st.err, e->stage_in, e->stage_out, e->plan_sb.p, e->en_sb.p, e->st.pins,
-                    e->st.xw_stats, (void*)e->st.rdesc, e->st.prio_seen};
+                    e->st.xw_stats, (void*)e->st.rdesc, e->st.prio_seen, e->en_report, e->agg,
+                    (void*)e->ts.rules, e->ts.fstate, (void*)e->ts.idtab, (void*)e->ts.ns, e->ts.lim, e->ts.cptab,
+                    (void*)e->ts.items, e->ts.rmulti, e->tok_stage, e->wire_arena, e->d_sum, e->en, e->en_acc,
+                    e->snap_counts, e->snap_offsets, e->snap_total, e->snap_rows, e->snap_scan, e->st.last_fetch,
+                    e->st.last_ts, e->nm_bytes, e->nm_off, e->nm_types, e->ml_mask, e->ml_counts, e->ml_offsets,
+                    e->ml_total, e->ml_rows, e->ml_keys, e->ml_order, e->ml_len, e->ml_off, e->ml_bytes, e->ml_out,
+                    e->ml_tmp, e->sys_plan, e->sys_pa, e->sys_pb, e->sys_mask, e->sys_ibuf, e->sx_msg, e->sx_recv,
+                    e->sx_seq, e->sx_ibuf, e->xmap_buf, e->xw_buf, e->st.xtab, e->ax_dir, e->st.ax_count,
+                    (void*)e->dg.rr_of, (void*)e->dg.off, (void*)e->dg.rules, e->dg.state, e->dgw.keys_in,
+                    e->dgw.keys_out, e->dgw.idx_in, e->dgw.idx_out, e->dgw.beg, e->dgw.end, e->dgw.sort_tmp,
+                    e->dgw.err, e->rh_err, e->dg_stage, e->dgw.heavy, e->dgw.n_heavy, e->dgw.sev, e->dgw.inv};
     for (void* p : ptrs) if (p) hipFree(p);
     for (void* p : e->user_allocs) hipFree(p);
     for (void* p : e->host_allocs) hipHostFree(p);
-    if (e->en_report) hipFree(e->en_report);
-    void* tptrs[] = {(void*)e->ts.rules, e->ts.fstate, (void*)e->ts.idtab, (void*)e->ts.ns, e->ts.lim, e->ts.cptab,
-                     (void*)e->ts.items, e->ts.rmulti, e->tok_stage, e->wire_arena, e->d_sum, e->en, e->en_acc, e->snap_counts, e->snap_offsets,
-                     e->snap_total, e->snap_rows, e->snap_scan, e->st.last_fetch, e->st.last_ts, e->nm_bytes, e->nm_off,
-                     e->nm_types, e->ml_mask, e->ml_counts, e->ml_offsets, e->ml_total, e->ml_rows, e->ml_keys,
-                     e->ml_order, e->ml_len, e->ml_off, e->ml_bytes, e->ml_out, e->ml_tmp};
-    for (void* p : tptrs) if (p) hipFree(p);
-    if (e->agg) hipFree(e->agg);
-    void* sptrs[] = {e->sys_plan, e->sys_pa, e->sys_pb, e->sys_mask, e->sys_ibuf, e->sx_msg, e->sx_recv,
-                     e->sx_seq, e->sx_ibuf};
-    for (void* p : sptrs) if (p) hipFree(p);
-    void* dptrs[] = {(void*)e->dg.rr_of, (void*)e->dg.off, (void*)e->dg.rules, e->dg.state, e->dgw.keys_in,
-                     e->dgw.keys_out, e->dgw.idx_in, e->dgw.idx_out, e->dgw.beg, e->dgw.end, e->dgw.sort_tmp,
-                     e->dgw.err, e->rh_err, e->dg_stage, e->dgw.heavy, e->dgw.n_heavy, e->dgw.sev, e->dgw.inv};
-    for (void* p : dptrs) if (p) hipFree(p);
-    void* xptrs[] = {e->xmap_buf, e->xw_buf, e->st.xtab, e->ax_dir, e->st.ax_count};
-    for (void* p : xptrs) if (p) hipFree(p);
     for (const AuxChunk& c : e->ax_host) hipFree(c.sec);          // (one allocation per chunk)
-    for (auto& p : e->pk) {
-        if (p.buf) hipFree(p.buf);
-        if (p.h2d) hipEventDestroy(p.h2d);
-        if (p.d2h) hipEventDestroy(p.d2h);
-        if (p.consumed) hipEventDestroy(p.consumed);
-        if (p.err_host) hipHostFree(p.err_host);
-        if (p.sp_counts) hipHostFree(p.sp_counts);
-    }
     if (e->h2d) { hipStreamSynchronize(e->h2d); hipStreamDestroy(e->h2d); }
     if (e->d2h) { hipStreamSynchronize(e->d2h); hipStreamDestroy(e->d2h); }
+    for (Slot& sl : e->slot) slot_destroy(sl);
     if (e->comm) ncclCommDestroy(e->comm);
     free_tok_work(e->tw);
-    for (auto& a : e->evs) for (auto& x : a) if (x) hipEventDestroy(x);
     for (auto& x : e->ml_ev) if (x) hipEventDestroy(x);
-    for (int k = 0; k < 2; k++) {
-        if (e->ev_sorted[k]) hipEventDestroy(e->ev_sorted[k]);
-        if (e->ev_done[k]) hipEventDestroy(e->ev_done[k]);
-        if (e->ev_end[k]) hipEventDestroy(e->ev_end[k]);
-        if (e->ev_core[k]) hipEventDestroy(e->ev_core[k]);
-    }
-    if (e->stream) hipStreamDestroy(e->stream);
-    if (e->stream2) hipStreamDestroy(e->stream2);
-    if (e->stream3) hipStreamDestroy(e->stream3);
-    if (e->stream4) hipStreamDestroy(e->stream4);
-    if (e->sstream) hipStreamDestroy(e->sstream);
+    for (hipStream_t x : {e->stream, e->stream2, e->stream3, e->stream4, e->sstream}) if (x) hipStreamDestroy(x);
     if (e->enstream && e->en_own) hipStreamDestroy(e->enstream);
     if (e->ev_en) hipEventDestroy(e->ev_en);
     delete e;
@@ -289,7 +297,7 @@ static int alloc_work(sf_engine* e, Work& w) {
     WALLOC(w.keys_in, N * 4); WALLOC(w.keys_out, N * 4); WALLOC(w.perm, N * 4);
     // (12-B payloads when the batch has origins)
     WALLOC(w.pv_in, N * sizeof(PackedEvO)); WALLOC(w.pv_out, N * sizeof(PackedEvO));
-    WALLOC(w.wide, 4); WALLOC(w.err, 4);
+    WALLOC(w.err, 4);
     WALLOC(w.head_scan, N * 4);
     WALLOC(w.seg_start, (N + 1) * 4); WALLOC(w.seg_res, N * 4); WALLOC(w.n_seg, 4);
     WALLOC(w.s_meta, N * 4);
@@ -405,13 +413,7 @@ int sf_create(const sf_config* cfg, sf_engine** out) {
         else e->side_mode = 0;
     }
     HIP_TRY(hipEventCreateWithFlags(&e->ev_en, hipEventDisableTiming));
-    for (auto& a : e->evs) for (auto& x : a) HIP_TRY(hipEventCreate(&x));
-    for (int k = 0; k < 2; k++) {
-        HIP_TRY(hipEventCreateWithFlags(&e->ev_sorted[k], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&e->ev_done[k], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&e->ev_end[k], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&e->ev_core[k], hipEventDisableTiming));
-    }
+    for (Slot& sl : e->slot) { const int rc = slot_create(sl); if (rc) { sf_destroy(e); return rc; } }
 
     DevState& st = e->st;
     st.S = c.sample_count; st.wl = c.interval_ms / c.sample_count; st.interval = c.interval_ms;
@@ -461,9 +463,9 @@ int sf_create(const sf_config* cfg, sf_engine** out) {
     HIP_TRY(launch_entry_init(e->en, st.max_rt, e->stream));
 
     {
-        const int rc = alloc_work(e, e->w[0]);
+        const int rc = alloc_work(e, e->slot[0].w);
         if (rc) { sf_destroy(e); return rc; }
-        e->w_ready[0] = true;
+        e->slot[0].ready = true;
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     *out = e;
@@ -476,12 +478,12 @@ static int local_of(const sf_engine* e, uint32_t res, uint32_t* l) {
     return *l < e->R;
 }
 
-// Per-kernel device times of the batch last run in Work set `slot` (its
-// events), added to the stats once, after that batch has completed.
-static void acc_timing(sf_engine* e, int slot) {
-    if (!e->timed[slot]) return;
-    e->timed[slot] = false;
-    hipEvent_t* ev = e->evs[slot];
+// Per-kernel device times of the batch last run in the slot (its events),
+// added to the stats once, after that batch has completed.
+static void acc_timing(sf_engine* e, Slot& sl) {
+    if (!sl.timed) return;
+    sl.timed = false;
+    hipEvent_t* ev = sl.evs;
     float a = 0, b2 = 0, c = 0, d = 0;
     hipEventElapsedTime(&a, ev[0], ev[1]);
     hipEventElapsedTime(&b2, ev[1], ev[2]);
@@ -506,11 +508,13 @@ static void acc_timing(sf_engine* e, int slot) {
     e->stats.total_ms += a + b2 + c + d;
 }
 
-static int sparse_complete(sf_engine::PkStage& pk);
-// Drain asynchronously submitted batches: wait for both streams, then report
-// the first error flag raised by any of them.  An async packed batch whose
-// verdicts the caller has not collected keeps its error for its own
-// sf_sync_packed, unless `all` (sf_sync: every batch collected here).
+// a batch's error flag (Work::err, read back after the batch) as the call's result
+static int batch_error(int err) {
+    if (!err) return SF_OK;
+    return fail(err, err == SF_ERR_CAPACITY ? "capacity exceeded (param table, or the origin / context node pool: aux_capacity)"
+                                            : "invalid batch (resource outside shard or bad entry_ref)");
+}
+
 // order `stream` after the last asynchronous ENTRY_NODE update (every host
 // call that reads or writes ENTRY_NODE on `stream` does this first)
 static int en_fence(sf_engine* e) {
@@ -520,38 +524,40 @@ static int en_fence(sf_engine* e) {
     return SF_OK;
 }
 
+static int sparse_complete(PkStage& pk);
+// Drain asynchronously submitted batches: wait for both streams, then report
+// the first error flag raised by any of them.  An async packed batch whose
+// verdicts the caller has not collected keeps its error for its own
+// sf_sync_packed, unless `all` (sf_sync: every batch collected here).
 static int drain(sf_engine* e, bool all = false) {
     if (e->en_async) { HIP_TRY(hipStreamSynchronize(e->enstream)); e->en_async = false; }
     if (!e->pending) return SF_OK;
     HIP_TRY(hipStreamSynchronize(e->sstream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (e->d2h) HIP_TRY(hipStreamSynchronize(e->d2h));
-    for (auto& p : e->pk) p.d2h_pending = false;
+    for (Slot& sl : e->slot) sl.pk.d2h_pending = false;
     int first = 0;
     unsigned keep = 0;
-    for (int k = 0; k < 2; k++) {
+    for (int k = 0; k < SF_SLOTS; k++) {
         if (!(e->pending & (1u << k))) continue;
+        PkStage& pk = e->slot[k].pk;
         // an async packed batch whose verdicts the caller has not collected: its
         // error came back with them and is reported by its own sf_sync_packed
-        if (e->pk[k].out_status && !all) { keep |= 1u << k; continue; }
-        if (e->pk[k].out_status) {
-            e->pk[k].out_status = nullptr;
-            if (e->pk[k].sparse) { const int rc = sparse_complete(e->pk[k]); if (rc) return rc; }
+        if (pk.out_status && !all) { keep |= 1u << k; continue; }
+        if (pk.out_status) {
+            pk.out_status = nullptr;
+            if (pk.sparse) { const int rc = sparse_complete(pk); if (rc) return rc; }
         }
         int32_t err = 0;
-        HIP_TRY(hipMemcpy(&err, e->w[k].err, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&err, e->slot[k].w.err, 4, hipMemcpyDeviceToHost));
         if (err && !first) first = err;
     }
     e->pending = keep;
-    for (int k = 0; k < 2; k++) acc_timing(e, k);
-    {
-        uint32_t nseg = 0;
-        HIP_TRY(hipMemcpy(&nseg, e->w[e->last].n_seg, 4, hipMemcpyDeviceToHost));
-        e->stats.n_segments = nseg;
-    }
-    if (first) return fail(first, first == SF_ERR_CAPACITY ? "capacity exceeded (param table, or the origin / context node pool: aux_capacity)"
-                                                           : "invalid batch (resource outside shard or bad entry_ref)");
-    return SF_OK;
+    for (Slot& sl : e->slot) acc_timing(e, sl);
+    uint32_t nseg = 0;
+    HIP_TRY(hipMemcpy(&nseg, e->slot[e->last].w.n_seg, 4, hipMemcpyDeviceToHost));
+    e->stats.n_segments = nseg;
+    return batch_error(first);
 }
 
 // The origin / context node pool and its index table (sf_xflow.h,
@@ -951,8 +957,8 @@ static int param_reserve(sf_engine* e, uint64_t bound) {
     // counters give the exact fill without a drain, and the pending worst-case
     // bounds are released (they only ever grew before).
     bool idle = true;
-    for (int k = 0; k < 2 && idle; k++)
-        if (e->used[k] && hipEventQuery(e->ev_done[k]) != hipSuccess) idle = false;
+    for (const Slot& sl : e->slot)
+        if (idle && sl.used && hipEventQuery(sl.done) != hipSuccess) idle = false;
     if (idle) {
         uint64_t used = 0;
         { const int rc = read_used(&used); if (rc) return rc; }
@@ -987,6 +993,7 @@ static int param_reserve(sf_engine* e, uint64_t bound) {
 static int stage_batch(sf_engine* e, const sf_event_batch* in, const sf_verdicts* out, hipStream_t ss,
                        DevBatch& b, DevVerdicts& dv) {
     const uint32_t n = in->n;
+    b.n = n; b.arg_slots = in->arg_slots; b.arg_stride = n;
     if (in->mem == SF_MEM_HOST) {
         size_t need = 0;
         size_t o_res = need; need += align_up((size_t)n * 4);
@@ -1057,13 +1064,91 @@ static int stage_batch(sf_engine* e, const sf_event_batch* in, const sf_verdicts
     return SF_OK;
 }
 
+// ---------------------------------------------------------------- stages of a submit (submit_core, sf_submit_node)
+static int check_event_batch(const sf_engine* e, const sf_event_batch* in) {
+    if (in->n && (!in->res_id || !in->ts_ms || !in->count || !in->flags)) return fail(SF_ERR_INVALID, "missing event array");
+    if (in->n > e->cfg.max_batch) return fail(SF_ERR_CAPACITY, "batch larger than max_batch");
+    if (in->arg_slots > SF_MAX_ARGS || (in->arg_slots && (!in->arg_tag || !in->arg_bits)))
+        return fail(SF_ERR_INVALID, "bad arg arrays");
+    if (in->arg_elem_off && in->n_elems && (!in->elem_tag || !in->elem_bits))
+        return fail(SF_ERR_INVALID, "collection arguments without element arrays");
+    return SF_OK;
+}
+
+// The origin-node pool on its first use (every entry with an origin has a node,
+// ClusterBuilderSlot.java:107-110; the caller has drained) and room in the
+// ParamFlow table for every key the batch can insert.
+static int reserve_for_batch(sf_engine* e, const sf_event_batch* in, bool with_ox) {
+    if (with_ox && !e->st.xtab) {
+        const int rc = ensure_aux(e);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    const uint64_t elems = in->arg_elem_off ? in->n_elems : 0;
+    return param_reserve(e, ((uint64_t)in->n + elems) * e->p_kmax);
+}
+
+// the batch that last used the next batch's slot (two submits ago) must be done:
+// its events and buffers are reused (sort(k) still overlaps decide(k-1))
+static int take_slot(sf_engine* e, Slot& sl) {
+    if (!sl.used) return SF_OK;
+    HIP_TRY(hipEventSynchronize(sl.done));
+    acc_timing(e, sl);
+    return SF_OK;
+}
+
+// the SystemRule planner's buffers and its verdicts (sf_system.h), on first use
+static int sys_buffers_ensure(sf_engine* e) {
+    if (!e->sys_plan) HIP_TRY(hipMalloc((void**)&e->sys_plan, sizeof(SysPlanDev)));
+    if (!e->sys_pa) HIP_TRY(hipMalloc((void**)&e->sys_pa, SYS_PLAN_BLOCKS * sizeof(SysExitQ)));
+    if (!e->sys_pb) HIP_TRY(hipMalloc((void**)&e->sys_pb, SYS_PLAN_BLOCKS * sizeof(SysEntQ)));
+    if (!e->sys_mask) HIP_TRY(hipMalloc((void**)&e->sys_mask, e->cfg.max_batch));
+    return SF_OK;
+}
+
+// the slot's batch is enqueued up to its last event record
+static void slot_enqueued(sf_engine* e, Slot& sl, uint32_t n) {
+    sl.used = true;
+    e->last = (int)(&sl - e->slot);
+    e->stats.n_events = n;
+    e->stats.n_launches++;
+}
+
+// The end of a synchronous batch on `stream`: its events, the verdicts back to
+// host arrays, its error flag, one stream sync.  plain: not the SystemRule
+// rounds (the segment count and kernel times of the batch go to the stats).
+static int finish_sync(sf_engine* e, Slot& sl, const sf_verdicts* out, const DevVerdicts& dv, uint32_t n, bool plain) {
+    hipStream_t s = e->stream;
+    HIP_TRY(hipEventRecord(sl.core, s));
+    HIP_TRY(hipEventRecord(sl.done, s));
+    HIP_TRY(hipEventRecord(sl.end, s));
+    slot_enqueued(e, sl, n);
+    sl.timed = plain && e->timing;
+    if (out->mem == SF_MEM_HOST && n) {
+        HIP_TRY(hipMemcpyAsync(out->status, dv.status, n, hipMemcpyDeviceToHost, s));
+        if (dv.wait) HIP_TRY(hipMemcpyAsync(out->wait_ms, dv.wait, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        if (dv.rule) HIP_TRY(hipMemcpyAsync(out->rule_idx, dv.rule, (size_t)n * 2, hipMemcpyDeviceToHost, s));
+    }
+    int32_t err = 0;
+    uint32_t nseg = 0;
+    HIP_TRY(hipMemcpyAsync(&err, sl.w.err, 4, hipMemcpyDeviceToHost, s));
+    if (plain) HIP_TRY(hipMemcpyAsync(&nseg, sl.w.n_seg, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (plain) {
+        e->stats.n_segments = nseg;
+        acc_timing(e, sl);
+    }
+    return batch_error(err);
+}
+
 // Sort and decide the view [p, q) of a staged batch (a SystemRule sub-batch):
 // its IN entries' system verdicts are in e->sys_mask, the verdicts of the
 // events before it in dv; stream e->stream (the caller fenced the batch's
 // staging).  v / dvv: the view, for the caller's ENTRY_NODE step.
-static int decide_view(sf_engine* e, Work& w, int slot, DevState& stl, const DevBatch& b, const DevVerdicts& dv,
+static int decide_view(sf_engine* e, Slot& sl, DevState& stl, const DevBatch& b, const DevVerdicts& dv,
                        uint32_t p, uint32_t q, bool with_ox, DevBatch& v, DevVerdicts& dvv) {
     hipStream_t s = e->stream;
+    Work& w = sl.w;
     v = b;
     v.n = q - p; v.base = p;
     v.res = b.res + p; v.ts = b.ts + p; v.cnt = b.cnt + p; v.flags = b.flags + p;
@@ -1073,7 +1158,7 @@ static int decide_view(sf_engine* e, Work& w, int slot, DevState& stl, const Dev
     v.origin = b.origin ? b.origin + p : nullptr; v.ctx = b.ctx ? b.ctx + p : nullptr;
     v.sys = e->sys_mask + p; v.vprev = dv.status + p;
     dvv = DevVerdicts{dv.status + p, dv.wait ? dv.wait + p : nullptr, dv.rule ? dv.rule + p : nullptr};
-    hipError_t le = launch_sort(stl, w, v, e->cfg.shard_count, e->cfg.shard_index, e->key_bits, s, e->evs[slot], false);
+    hipError_t le = launch_sort(stl, w, v, e->cfg.shard_count, e->cfg.shard_index, e->key_bits, s, sl.evs, false);
     OxPlan plan{};
     if (le == hipSuccess && with_ox) {
         const int rc = prepare_origins(e, w, v, s, &plan);
@@ -1082,7 +1167,7 @@ static int decide_view(sf_engine* e, Work& w, int slot, DevState& stl, const Dev
     }
     if (le == hipSuccess)
         le = launch_decide(stl, w, v, dvv, s, e->serial ? s : e->stream2, e->serial ? s : e->stream3,
-                           e->serial ? s : e->stream4, e->evs[slot], false, with_ox ? &plan : nullptr);
+                           e->serial ? s : e->stream4, sl.evs, false, with_ox ? &plan : nullptr);
     if (le == hipSuccess && with_ox) w.ox_dirty = false;     // k_ox_reset enqueued
     if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("launch: ") + hipGetErrorString(le));
     return SF_OK;
@@ -1091,134 +1176,96 @@ static int decide_view(sf_engine* e, Work& w, int slot, DevState& stl, const Dev
 // pre: launched on the sort stream after the batch's error flag is cleared and
 // before its sort (sf_submit_packed's expansion of the packed words)
 using PreSort = std::function<hipError_t(hipStream_t, int32_t*)>;
+
+// A staged batch under SystemRules on an unsharded engine.  They couple every
+// IN entry to the global ENTRY_NODE: the batch is decided as a sequence of
+// safe sub-batches (sf_system.h), each planned on the exact ENTRY_NODE, then
+// sorted / decided / reduced by the ordinary pipeline.  One host round trip
+// per sub-batch (its end q).
+static int submit_sys_rounds(sf_engine* e, Slot& sl, const DevBatch& b, const DevVerdicts& dv, const sf_verdicts* out,
+                             bool with_ox, const PreSort* pre) {
+    const uint32_t n = b.n;
+    hipStream_t s = e->stream, ss = e->serial ? e->stream : e->sstream;
+    Work& w = sl.w;
+    { const int rc = sys_buffers_ensure(e); if (rc) return rc; }
+    if (!e->sys_ibuf && e->st.n_prule) HIP_TRY(hipMalloc((void**)&e->sys_ibuf, SYS_PLAN_CAP));
+    HIP_TRY(hipMemsetAsync(w.err, 0, sizeof(int32_t), ss));
+    if (pre) {
+        const hipError_t pe = (*pre)(ss, w.err);
+        if (pe != hipSuccess) return fail(SF_ERR_DEVICE, std::string("pre-sort: ") + hipGetErrorString(pe));
+    }
+    HIP_TRY(hipEventRecord(sl.sorted, ss));
+    HIP_TRY(hipStreamWaitEvent(s, sl.sorted, 0));
+    { const int rc = en_fence(e); if (rc) return rc; }
+    DevState stl = e->st;
+    stl.err = w.err;
+    uint32_t p = 0, rounds = 0;
+    while (p < n) {
+        hipError_t le = sys_plan(stl, b, dv.status, e->sys_mask, e->sys, e->en, p, e->sys_plan, e->sys_pa,
+                                 e->sys_pb, s, e->sys_ibuf);
+        if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("system plan: ") + hipGetErrorString(le));
+        uint32_t qi[2] = {0, 0};                        // q, inert entries planned
+        static_assert(offsetof(SysPlanDev, n_inert) == offsetof(SysPlanDev, q) + 4, "q, n_inert adjacent");
+        HIP_TRY(hipMemcpyAsync(qi, &e->sys_plan->q, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        const uint32_t q = qi[0];
+        if (q <= p || q > n) return fail(SF_ERR_DEVICE, "system planner made no progress");
+        DevBatch v;
+        DevVerdicts dvv;
+        { const int rc = decide_view(e, sl, stl, b, dv, p, q, with_ox, v, dvv); if (rc) return rc; }
+        // the system verdicts of the inert entries (ENTRY_NODE is still at p)
+        if (qi[1]) le = sys_plan_fix(stl, b, dv, e->sys_mask, e->sys, p, q, e->sys_plan, e->sys_pa, e->sys_pb, s);
+        if (le == hipSuccess) le = launch_entry_node(stl, v, dvv.status, e->en, e->en_acc, s);
+        if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("launch: ") + hipGetErrorString(le));
+        p = q;
+        rounds++;
+    }
+    e->stats.sys_rounds += rounds;
+    return finish_sync(e, sl, out, dv, n, false);
+}
+
 static int submit_core(sf_engine* e, const sf_event_batch* in, sf_verdicts* out, bool async,
                        const uint8_t* forced = nullptr, const PreSort* pre = nullptr) {
     if (!e || !in || !out || !out->status) return fail(SF_ERR_INVALID, "null argument");
     if (in->n == 0) return SF_OK;
-    if (!in->res_id || !in->ts_ms || !in->count || !in->flags) return fail(SF_ERR_INVALID, "missing event array");
-    if (in->n > e->cfg.max_batch) return fail(SF_ERR_CAPACITY, "batch larger than max_batch");
-    if (in->arg_slots > SF_MAX_ARGS || (in->arg_slots && (!in->arg_tag || !in->arg_bits)))
-        return fail(SF_ERR_INVALID, "bad arg arrays");
-    if (in->arg_elem_off && in->n_elems && (!in->elem_tag || !in->elem_bits))
-        return fail(SF_ERR_INVALID, "collection arguments without element arrays");
+    { const int rc = check_event_batch(e, in); if (rc) return rc; }
     // SystemRules read the node-wide ENTRY_NODE: a sharded engine decides them
     // only through the round protocol (sf_system_plan / sf_submit_forced)
     if (e->sys.check && e->cfg.shard_count > 1 && !forced)
         return fail(SF_ERR_UNSUPPORTED, "SystemRules on a sharded engine: use sf_system_plan + sf_submit_forced "
                                         "+ sf_entry_node_add (the node-wide round protocol)");
     const uint32_t n = in->n;
-    DevBatch b{};
-    b.n = n; b.arg_slots = in->arg_slots;
     hipStream_t s = e->stream, ss = e->serial ? e->stream : e->sstream;
-    if ((in->origin || e->st.xmap) && !e->st.xtab) {
-        // the first batch with origins: the origin-node pool (every entry with an
-        // origin has one, ClusterBuilderSlot.java:107-110)
-        { const int rc = drain(e); if (rc) return rc; }
-        const int rc = ensure_aux(e);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
     // the origin-node pass (sf_origin.hip) runs for batches with origins and
     // whenever rules read origin / context nodes (the xflow walk's node keys)
     const bool with_ox = in->origin || e->st.xmap;
     // asynchronous only for HBM-resident batches and verdicts, without SystemRules
     async = async && in->mem != SF_MEM_HOST && out->mem != SF_MEM_HOST && !e->sys.check && !forced;
-    if (!async) { const int rc = drain(e); if (rc) return rc; }
-    {   // room in the ParamFlow table for every key this batch can insert
-        const uint64_t elems = in->arg_elem_off ? in->n_elems : 0;
-        const int rc = param_reserve(e, ((uint64_t)n + elems) * e->p_kmax);
-        if (rc) return rc;
-    }
-    if (async && !e->w_ready[1]) {                 // second Work set on first asynchronous use
+    // (the first batch with origins builds the origin-node pool with nothing in flight)
+    if (!async || (with_ox && !e->st.xtab)) { const int rc = drain(e); if (rc) return rc; }
+    { const int rc = reserve_for_batch(e, in, with_ox); if (rc) return rc; }
+    for (Slot& x : e->slot) {                      // the other Work sets on first asynchronous use
+        if (!async || x.ready) continue;
         HIP_TRY(hipStreamSynchronize(s));
-        const int rc = alloc_work(e, e->w[1]);
-        if (rc) return rc;
-        e->w_ready[1] = true;
+        { const int rc = alloc_work(e, x.w); if (rc) return rc; }
+        x.ready = true;
     }
-    const int slot = e->cur;
-    Work& w = e->w[slot];
-    if (e->used[slot]) {
-        // the batch that last used this Work set (two submits ago) must be done:
-        // its events and buffers are reused (sort(k) still overlaps decide(k-1))
-        HIP_TRY(hipEventSynchronize(e->ev_done[slot]));
-        acc_timing(e, slot);
-    }
+    Slot& sl = e->slot[e->cur];
+    { const int rc = take_slot(e, sl); if (rc) return rc; }
+    Work& w = sl.w;
+    DevBatch b{};
     DevVerdicts dv{};
     { const int rc = stage_batch(e, in, out, ss, b, dv); if (rc) return rc; }
-    b.arg_stride = n;
     if (forced) {
         // the forced SystemRule verdicts of this (sub-)batch, planned node-wide
-        if (!e->sys_mask) HIP_TRY(hipMalloc((void**)&e->sys_mask, e->cfg.max_batch));
-        HIP_TRY(hipMemcpyAsync(e->sys_mask, forced, n, hipMemcpyHostToDevice, e->serial ? e->stream : e->sstream));
+        { const int rc = sys_buffers_ensure(e); if (rc) return rc; }
+        HIP_TRY(hipMemcpyAsync(e->sys_mask, forced, n, hipMemcpyHostToDevice, ss));
         b.sys = e->sys_mask;
     }
-    if (e->sys.check && !forced) {
-        // SystemRules couple every IN entry to the global ENTRY_NODE: the batch
-        // is decided as a sequence of safe sub-batches (sf_system.h), each
-        // planned on the exact ENTRY_NODE, then sorted / decided / reduced by
-        // the ordinary pipeline.  One host round trip per sub-batch (its end q).
-        if (!e->sys_plan) {
-            HIP_TRY(hipMalloc((void**)&e->sys_plan, sizeof(SysPlanDev)));
-            HIP_TRY(hipMalloc((void**)&e->sys_pa, SYS_PLAN_BLOCKS * sizeof(SysExitQ)));
-            HIP_TRY(hipMalloc((void**)&e->sys_pb, SYS_PLAN_BLOCKS * sizeof(SysEntQ)));
-            HIP_TRY(hipMalloc((void**)&e->sys_mask, e->cfg.max_batch));
-        }
-        if (!e->sys_ibuf && e->st.n_prule) HIP_TRY(hipMalloc((void**)&e->sys_ibuf, SYS_PLAN_CAP));
-        HIP_TRY(hipMemsetAsync(w.err, 0, sizeof(int32_t), ss));
-        if (pre) {
-            const hipError_t pe = (*pre)(ss, w.err);
-            if (pe != hipSuccess) return fail(SF_ERR_DEVICE, std::string("pre-sort: ") + hipGetErrorString(pe));
-        }
-        HIP_TRY(hipEventRecord(e->ev_sorted[slot], ss));
-        HIP_TRY(hipStreamWaitEvent(s, e->ev_sorted[slot], 0));
-        { const int rc = en_fence(e); if (rc) return rc; }
-        DevState stl = e->st;
-        stl.err = w.err;
-        uint32_t p = 0, rounds = 0;
-        while (p < n) {
-            hipError_t le = sys_plan(stl, b, dv.status, e->sys_mask, e->sys, e->en, p, e->sys_plan, e->sys_pa,
-                                     e->sys_pb, s, e->sys_ibuf);
-            if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("system plan: ") + hipGetErrorString(le));
-            uint32_t qi[2] = {0, 0};                        // q, inert entries planned
-            static_assert(offsetof(SysPlanDev, n_inert) == offsetof(SysPlanDev, q) + 4, "q, n_inert adjacent");
-            HIP_TRY(hipMemcpyAsync(qi, &e->sys_plan->q, 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            const uint32_t q = qi[0];
-            if (q <= p || q > n) return fail(SF_ERR_DEVICE, "system planner made no progress");
-            DevBatch v;
-            DevVerdicts dvv;
-            { const int rc = decide_view(e, w, slot, stl, b, dv, p, q, with_ox, v, dvv); if (rc) return rc; }
-            // the system verdicts of the inert entries (ENTRY_NODE is still at p)
-            if (le == hipSuccess && qi[1])
-                le = sys_plan_fix(stl, b, dv, e->sys_mask, e->sys, p, q, e->sys_plan, e->sys_pa, e->sys_pb, s);
-            if (le == hipSuccess) le = launch_entry_node(stl, v, dvv.status, e->en, e->en_acc, s);
-            if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("launch: ") + hipGetErrorString(le));
-            p = q;
-            rounds++;
-        }
-        HIP_TRY(hipEventRecord(e->ev_core[slot], s));
-        HIP_TRY(hipEventRecord(e->ev_done[slot], s));
-    HIP_TRY(hipEventRecord(e->ev_end[slot], s));
-        e->used[slot] = true;
-        e->last = slot;
-        e->stats.n_events = n;
-        e->stats.n_launches++;
-        e->stats.sys_rounds += rounds;
-        if (out->mem == SF_MEM_HOST) {
-            HIP_TRY(hipMemcpyAsync(out->status, dv.status, n, hipMemcpyDeviceToHost, s));
-            if (dv.wait) HIP_TRY(hipMemcpyAsync(out->wait_ms, dv.wait, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-            if (dv.rule) HIP_TRY(hipMemcpyAsync(out->rule_idx, dv.rule, (size_t)n * 2, hipMemcpyDeviceToHost, s));
-        }
-        int32_t err = 0;
-        HIP_TRY(hipMemcpyAsync(&err, w.err, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (err) return fail(err, err == SF_ERR_CAPACITY ? "capacity exceeded (param table, or the origin / context node pool: aux_capacity)"
-                                                         : "invalid batch (resource outside shard or bad entry_ref)");
-        return SF_OK;
-    }
+    if (e->sys.check && !forced) return submit_sys_rounds(e, sl, b, dv, out, with_ox, pre);
     // sort phase on the sort stream, into this batch's Work set (after the
     // decide phase of the batch that used it last)
-    if (e->used[slot]) HIP_TRY(hipStreamWaitEvent(ss, e->ev_done[slot], 0));
+    if (sl.used) HIP_TRY(hipStreamWaitEvent(ss, sl.done, 0));
     HIP_TRY(hipMemsetAsync(w.err, 0, sizeof(int32_t), ss));
     if (pre) {
         const hipError_t pe = (*pre)(ss, w.err);
@@ -1226,7 +1273,7 @@ static int submit_core(sf_engine* e, const sf_event_batch* in, sf_verdicts* out,
     }
     DevState stl = e->st;
     stl.err = w.err;
-    hipError_t le = launch_sort(stl, w, b, e->cfg.shard_count, e->cfg.shard_index, e->key_bits, ss, e->evs[slot], e->timing);
+    hipError_t le = launch_sort(stl, w, b, e->cfg.shard_count, e->cfg.shard_index, e->key_bits, ss, sl.evs, e->timing);
     if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("launch: ") + hipGetErrorString(le));
     OxPlan plan{};
     if (with_ox) {
@@ -1234,64 +1281,41 @@ static int submit_core(sf_engine* e, const sf_event_batch* in, sf_verdicts* out,
         if (rc) return rc;
         stl.xtab = e->st.xtab; stl.xcap_mask = e->st.xcap_mask; stl.ax_cap = e->st.ax_cap;
     }
-    HIP_TRY(hipEventRecord(e->ev_sorted[slot], ss));
+    HIP_TRY(hipEventRecord(sl.sorted, ss));
     // decide phase in batch order on the main streams
-    HIP_TRY(hipStreamWaitEvent(s, e->ev_sorted[slot], 0));
+    HIP_TRY(hipStreamWaitEvent(s, sl.sorted, 0));
     // an asynchronous batch's verdict scatter and ENTRY_NODE update run on the
     // ENTRY_NODE stream, beside the next batch's decide phase
-    const bool side = !forced && async && !e->serial && e->side_mode != 0;
+    const bool side = async && !e->serial && e->side_mode != 0;
     le = launch_decide(stl, w, b, dv, s, e->serial ? s : e->stream2, e->serial ? s : e->stream3,
-                       e->serial ? s : e->stream4, e->evs[slot], e->timing,
+                       e->serial ? s : e->stream4, sl.evs, e->timing,
                        with_ox ? &plan : nullptr, false, side ? e->enstream : nullptr);
     if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("launch: ") + hipGetErrorString(le));
     if (with_ox) w.ox_dirty = false;                                  // k_ox_reset enqueued
     // ENTRY_NODE: every IN event's StatisticSlot updates (after the verdicts, stream
     // order); under the round protocol the node-wide stream updates it (sf_entry_node_add)
-    if (side) {
-        // asynchronous: on the side stream after the scatter.  The Work set is
-        // free after the scatter (ev_done: the sort of the batch after next waits
-        // for it), the batch k_entry_acc reads after the update (ev_end)
-        HIP_TRY(hipEventRecord(e->ev_core[slot], e->enstream));
-        HIP_TRY(hipEventRecord(e->ev_done[slot], e->enstream));
-        le = launch_entry_node(stl, b, dv.status, e->en, e->en_acc, e->enstream);
+    if (!side && !forced) {
+        { const int rc = en_fence(e); if (rc) return rc; }
+        le = launch_entry_node(stl, b, dv.status, e->en, e->en_acc, s);
         if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("entry node: ") + hipGetErrorString(le));
-        HIP_TRY(hipEventRecord(e->ev_end[slot], e->enstream));
-        HIP_TRY(hipEventRecord(e->ev_en, e->enstream));
-        e->en_async = true;
-    } else {
-        if (!forced) {
-            { const int rc = en_fence(e); if (rc) return rc; }
-            le = launch_entry_node(stl, b, dv.status, e->en, e->en_acc, s);
-            if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("entry node: ") + hipGetErrorString(le));
-        }
-        HIP_TRY(hipEventRecord(e->ev_core[slot], s));
-        HIP_TRY(hipEventRecord(e->ev_done[slot], s));
-    HIP_TRY(hipEventRecord(e->ev_end[slot], s));
     }
-    e->used[slot] = true;
-    e->timed[slot] = e->timing;
-    e->last = slot;
-    e->stats.n_events = n;
-    e->stats.n_launches++;
-    if (async) {
-        e->pending |= 1u << slot;
-        e->cur ^= 1;
-        return SF_OK;
+    if (!async) return finish_sync(e, sl, out, dv, n, true);
+    // side: on the side stream after the scatter.  The Work set is free after
+    // the scatter (done: the sort of the batch after next waits for it), the
+    // batch k_entry_acc reads after the update (end)
+    hipStream_t es = side ? e->enstream : s;
+    HIP_TRY(hipEventRecord(sl.core, es));
+    HIP_TRY(hipEventRecord(sl.done, es));
+    if (side) {
+        le = launch_entry_node(stl, b, dv.status, e->en, e->en_acc, es);
+        if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("entry node: ") + hipGetErrorString(le));
     }
-    if (out->mem == SF_MEM_HOST) {
-        HIP_TRY(hipMemcpyAsync(out->status, dv.status, n, hipMemcpyDeviceToHost, s));
-        if (dv.wait) HIP_TRY(hipMemcpyAsync(out->wait_ms, dv.wait, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        if (dv.rule) HIP_TRY(hipMemcpyAsync(out->rule_idx, dv.rule, (size_t)n * 2, hipMemcpyDeviceToHost, s));
-    }
-    int32_t err = 0;
-    uint32_t nseg = 0;
-    HIP_TRY(hipMemcpyAsync(&err, w.err, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&nseg, w.n_seg, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    e->stats.n_segments = nseg;
-    acc_timing(e, slot);
-    if (err) return fail(err, err == SF_ERR_CAPACITY ? "capacity exceeded (param table, or the origin / context node pool: aux_capacity)"
-                                                     : "invalid batch (resource outside shard or bad entry_ref)");
+    HIP_TRY(hipEventRecord(sl.end, es));
+    if (side) { HIP_TRY(hipEventRecord(e->ev_en, es)); e->en_async = true; }
+    slot_enqueued(e, sl, n);
+    sl.timed = e->timing;
+    e->pending |= 1u << e->cur;
+    e->cur = (e->cur + 1) % SF_SLOTS;
     return SF_OK;
 }
 
@@ -1313,7 +1337,7 @@ int sf_submit_async(sf_engine* e, const sf_event_batch* in, sf_verdicts* out) {
 // on the sort stream, decided by submit_core (asynchronously when asked), and
 // the verdicts come back on the D2H stream once the batch is decided.
 // the rest of a sparse batch's lists (beyond the prefetch) and their lengths, once its copies are done
-static int sparse_complete(sf_engine::PkStage& pk) {
+static int sparse_complete(PkStage& pk) {
     const uint32_t nw = pk.sp_counts[0], nr = pk.sp_counts[1], pre = pk.sp.prefetch;
     if (nw > pre) HIP_TRY(hipMemcpy(pk.sp.waits + pre, pk.sp_wl + pre, (size_t)(nw - pre) * 8, hipMemcpyDeviceToHost));
     if (nr > pre) HIP_TRY(hipMemcpy(pk.sp.rules + pre, pk.sp_rl + pre, (size_t)(nr - pre) * 8, hipMemcpyDeviceToHost));
@@ -1339,7 +1363,8 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
     if (!e->h2d) {
         HIP_TRY(hipStreamCreateWithFlags(&e->h2d, hipStreamNonBlocking));
         HIP_TRY(hipStreamCreateWithFlags(&e->d2h, hipStreamNonBlocking));
-        for (auto& p : e->pk) {
+        for (Slot& x : e->slot) {
+            PkStage& p = x.pk;
             HIP_TRY(hipEventCreateWithFlags(&p.h2d, hipEventDisableTiming));
             HIP_TRY(hipEventCreateWithFlags(&p.d2h, hipEventDisableTiming));
             HIP_TRY(hipEventCreateWithFlags(&p.consumed, hipEventDisableTiming));
@@ -1351,8 +1376,8 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
     // (submit_core decides asynchronously only without SystemRules; the slot it takes is e->cur)
     const bool core_async = async && !e->sys.check;
     if (!core_async) { const int rc = drain(e); if (rc) return rc; }
-    const int slot = e->cur;
-    auto& pk = e->pk[slot];
+    Slot& sl = e->slot[e->cur];
+    PkStage& pk = sl.pk;
     // The slot's staging buffer: its packed inputs are free once the batch
     // before in this slot has expanded them (early in its sort phase), its
     // expanded arrays once that batch is decided (submit_core waits for it
@@ -1370,7 +1395,7 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
     const size_t o_wl = sp ? take(N * 8) : 0, o_rl = sp ? take(N * 8) : 0, o_sc = sp ? take(16) : 0;
     const size_t o_ms = narrow ? take((size_t)SF_PK4_MAX_MS * 4) : 0;   // (the narrow words use o_ev's room)
     if (pk.bytes < off) {
-        if (e->used[slot]) HIP_TRY(hipEventSynchronize(e->ev_end[slot]));
+        if (sl.used) HIP_TRY(hipEventSynchronize(sl.end));
         if (pk.consumed_pending) { HIP_TRY(hipEventSynchronize(pk.consumed)); pk.consumed_pending = false; }
         if (pk.d2h_pending) { HIP_TRY(hipEventSynchronize(pk.d2h)); pk.d2h_pending = false; }
         if (pk.buf) hipFree(pk.buf);
@@ -1442,13 +1467,13 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
     dv.rule_idx = (sp || out->rule_idx) ? (host_out ? (uint16_t*)(B + o_ru) : out->rule_idx) : nullptr;
     // (the expansion rewrites the arrays the ENTRY_NODE update of this slot's
     // previous batch reads)
-    if (e->used[slot]) HIP_TRY(hipStreamWaitEvent(ss, e->ev_end[slot], 0));
+    if (sl.used) HIP_TRY(hipStreamWaitEvent(ss, sl.end, 0));
     const int rc = submit_core(e, &eb, &dv, core_async, nullptr, &expand);
     if (rc) return rc;
     pk.consumed_pending = true;
     if (host_out) {
         hipStream_t d = e->serial ? e->stream : e->d2h;
-        HIP_TRY(hipStreamWaitEvent(d, e->ev_core[slot], 0));
+        HIP_TRY(hipStreamWaitEvent(d, sl.core, 0));
         HIP_TRY(hipMemcpyAsync(out->status, dv.status, n, hipMemcpyDeviceToHost, d));
         pk.sparse = sp != nullptr;
         if (sp) {
@@ -1469,7 +1494,7 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
             if (out->wait_ms) HIP_TRY(hipMemcpyAsync(out->wait_ms, dv.wait_ms, (size_t)n * 4, hipMemcpyDeviceToHost, d));
             if (out->rule_idx) HIP_TRY(hipMemcpyAsync(out->rule_idx, dv.rule_idx, (size_t)n * 2, hipMemcpyDeviceToHost, d));
         }
-        if (core_async) HIP_TRY(hipMemcpyAsync(pk.err_host, e->w[slot].err, 4, hipMemcpyDeviceToHost, d));
+        if (core_async) HIP_TRY(hipMemcpyAsync(pk.err_host, sl.w.err, 4, hipMemcpyDeviceToHost, d));
         HIP_TRY(hipEventRecord(pk.d2h, d));
         pk.d2h_pending = true;
         pk.out_status = core_async ? out->status : nullptr;
@@ -1495,8 +1520,8 @@ int sf_submit_packed_async(sf_engine* e, const sf_packed_batch* in, sf_verdicts*
 // verdicts.  A batch already collected (by sf_sync, a rule reload's drain, or
 // an earlier call) has nothing left to wait for: SF_OK.
 static int sync_packed(sf_engine* e, const uint8_t* status) {
-    for (int k = 0; k < 2; k++) {
-        auto& pk = e->pk[k];
+    for (int k = 0; k < SF_SLOTS; k++) {
+        PkStage& pk = e->slot[k].pk;
         if (!status || pk.out_status != status) continue;
         // (a drain may have waited for its copies already; its error stays this batch's)
         if (pk.d2h_pending) HIP_TRY(hipEventSynchronize(pk.d2h));
@@ -1504,10 +1529,7 @@ static int sync_packed(sf_engine* e, const uint8_t* status) {
         pk.out_status = nullptr;
         e->pending &= ~(1u << k);          // checked here, not again by sf_sync
         if (pk.sparse) { const int rc = sparse_complete(pk); if (rc) return rc; }
-        const int32_t err = *pk.err_host;
-        if (err) return fail(err, err == SF_ERR_CAPACITY ? "capacity exceeded (param table, or the origin / context node pool: aux_capacity)"
-                                                         : "invalid batch (resource outside shard or bad entry_ref)");
-        return SF_OK;
+        return batch_error(*pk.err_host);
     }
     return SF_OK;
 }
@@ -1633,13 +1655,8 @@ static int sx_recv_reserve(sf_engine* e, size_t words) {
 int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, sf_verdicts* out,
                    sf_allgather_fn allgather, void* ctx) {
     if (!e || !in || !out) return fail(SF_ERR_INVALID, "null argument");
-    if (in->n && (!seq || !out->status || !in->res_id || !in->ts_ms || !in->count || !in->flags))
-        return fail(SF_ERR_INVALID, "missing event array");
-    if (in->n > e->cfg.max_batch) return fail(SF_ERR_CAPACITY, "batch larger than max_batch");
-    if (in->arg_slots > SF_MAX_ARGS || (in->arg_slots && (!in->arg_tag || !in->arg_bits)))
-        return fail(SF_ERR_INVALID, "bad arg arrays");
-    if (in->arg_elem_off && in->n_elems && (!in->elem_tag || !in->elem_bits))
-        return fail(SF_ERR_INVALID, "collection arguments without element arrays");
+    if (in->n && (!seq || !out->status)) return fail(SF_ERR_INVALID, "missing event array");
+    { const int rc = check_event_batch(e, in); if (rc) return rc; }
     std::lock_guard<std::mutex> lk(e->mu);
     if (!e->sys.check) return in->n ? submit_core(e, in, out, false) : SF_OK;   // nothing node-wide to decide
     if (!sx_rule_ok(e->sys))
@@ -1653,23 +1670,16 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
         HIP_TRY(hipMalloc((void**)&e->sx_msg, SX_WORDS * 8));
         HIP_TRY(hipMalloc((void**)&e->sx_ibuf, e->cfg.max_batch));
     }
-    if (!e->sys_mask) HIP_TRY(hipMalloc((void**)&e->sys_mask, e->cfg.max_batch));
+    { const int rc = sys_buffers_ensure(e); if (rc) return rc; }
     { const int rc = sx_recv_reserve(e, (size_t)N * SX_WORDS); if (rc) return rc; }
     const bool with_ox = in->origin || e->st.xmap;
-    if (with_ox && !e->st.xtab) { const int rc = ensure_aux(e); if (rc) return rc; HIP_TRY(hipStreamSynchronize(s)); }
-    {
-        const uint64_t elems = in->arg_elem_off ? in->n_elems : 0;
-        const int rc = param_reserve(e, ((uint64_t)n + elems) * e->p_kmax);
-        if (rc) return rc;
-    }
-    const int slot = e->cur;
-    Work& w = e->w[slot];
-    if (e->used[slot]) { HIP_TRY(hipEventSynchronize(e->ev_done[slot])); acc_timing(e, slot); }
+    { const int rc = reserve_for_batch(e, in, with_ox); if (rc) return rc; }
+    Slot& sl = e->slot[e->cur];
+    { const int rc = take_slot(e, sl); if (rc) return rc; }
+    Work& w = sl.w;
     DevBatch b{};
-    b.n = n; b.arg_slots = in->arg_slots;
     DevVerdicts dv{};
     { const int rc = stage_batch(e, in, out, s, b, dv); if (rc) return rc; }
-    b.arg_stride = n;
     const int64_t* dseq = seq;
     if (in->mem == SF_MEM_HOST && n) {
         if (!e->sx_seq) HIP_TRY(hipMalloc((void**)&e->sx_seq, (size_t)e->cfg.max_batch * 8));
@@ -1785,7 +1795,7 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
             if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("exchange mask: ") + hipGetErrorString(le));
             DevBatch v;
             DevVerdicts dvv;
-            { const int rc = decide_view(e, w, slot, stl, b, dv, lp, lq, with_ox, v, dvv); if (rc) return rc; }
+            { const int rc = decide_view(e, sl, stl, b, dv, lp, lq, with_ox, v, dvv); if (rc) return rc; }
             le = launch_entry_delta(stl, v, dvv.status, e->en_acc, e->sx_msg, wkey[j], s);
             if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("exchange delta: ") + hipGetErrorString(le));
         } else {
@@ -1795,28 +1805,13 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
         sp = hp.q;
         rounds++;
     }
-    HIP_TRY(hipMemcpyAsync(e->en, &enh, sizeof enh, hipMemcpyHostToDevice, s));
     if (lp != n) return fail(SF_ERR_DEVICE, "exchange rounds left events undecided");
-    HIP_TRY(hipEventRecord(e->ev_core[slot], s));
-    HIP_TRY(hipEventRecord(e->ev_done[slot], s));
-    HIP_TRY(hipEventRecord(e->ev_end[slot], s));
-    e->used[slot] = true;
-    e->last = slot;
-    e->stats.n_events = n;
-    e->stats.n_launches++;
+    // (enh lives in this frame: the copy is complete before any return)
+    HIP_TRY(hipMemcpyAsync(e->en, &enh, sizeof enh, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
     e->stats.sys_rounds += rounds;
     e->stats.sys_exchanges += levels;
-    if (out->mem == SF_MEM_HOST && n) {
-        HIP_TRY(hipMemcpyAsync(out->status, dv.status, n, hipMemcpyDeviceToHost, s));
-        if (dv.wait) HIP_TRY(hipMemcpyAsync(out->wait_ms, dv.wait, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        if (dv.rule) HIP_TRY(hipMemcpyAsync(out->rule_idx, dv.rule, (size_t)n * 2, hipMemcpyDeviceToHost, s));
-    }
-    int32_t err = 0;
-    HIP_TRY(hipMemcpyAsync(&err, w.err, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (err) return fail(err, err == SF_ERR_CAPACITY ? "capacity exceeded (param table, or the origin / context node pool: aux_capacity)"
-                                                     : "invalid batch (resource outside shard or bad entry_ref)");
-    return SF_OK;
+    return finish_sync(e, sl, out, dv, n, false);
 }
 
 int sf_system_plan(sf_engine* e, const sf_event_batch* in, const uint8_t* status, uint32_t p, uint32_t* q,
@@ -1834,12 +1829,7 @@ int sf_system_plan(sf_engine* e, const sf_event_batch* in, const uint8_t* status
         *q = n;
         return SF_OK;
     }
-    if (!e->sys_plan) {
-        HIP_TRY(hipMalloc((void**)&e->sys_plan, sizeof(SysPlanDev)));
-        HIP_TRY(hipMalloc((void**)&e->sys_pa, SYS_PLAN_BLOCKS * sizeof(SysExitQ)));
-        HIP_TRY(hipMalloc((void**)&e->sys_pb, SYS_PLAN_BLOCKS * sizeof(SysEntQ)));
-        HIP_TRY(hipMalloc((void**)&e->sys_mask, e->cfg.max_batch));
-    }
+    { const int rc = sys_buffers_ensure(e); if (rc) return rc; }
     DevBatch b;
     uint8_t* dstatus = nullptr;
     // a later round of the same merged stream (p > 0, same arrays): the events
@@ -2793,7 +2783,7 @@ int sf_heavy_profile_read(sf_engine* e, sf_heavy_profile* out, uint32_t cap, uin
     std::lock_guard<std::mutex> g(e->mu);
     uint32_t cnt[7] = {0, 0, 0, 0, 0, 0, 0}, nseg = 0;
     { const int rc = drain(e); if (rc) return rc; }
-    const Work& lw = e->w[e->last];
+    const Work& lw = e->slot[e->last].w;
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream2));
     HIP_TRY(hipStreamSynchronize(e->stream3));

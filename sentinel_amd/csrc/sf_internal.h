@@ -212,7 +212,6 @@ struct Work {
     uint32_t* keys_in;   uint32_t* keys_out;     // local resource id
     uint32_t* perm;                              // sorted position -> submission index
     PackedEv* pv_in; PackedEv* pv_out;           // sort payload
-    uint32_t* wide;                              // (unused)
     int32_t* err;                                // batch error flag (this Work set's batch)
     bool ox_dirty;                               // index pass ran, origin apply (k_ox_reset) not enqueued
     uint32_t* head;      uint32_t* head_scan;    // segment flags and positions

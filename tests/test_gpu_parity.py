@@ -162,6 +162,53 @@ def test_async_pipelined_batches(eng_mod, so, split):
     parity.compare_verdicts(e.submit(shifted), ora.submit(shifted), "sync after async")
 
 
+def test_slot_recycling_across_paths(eng_mod, so):
+    """One engine's slots reused across the submit paths: a sync submit, three
+    async device batches (both slots taken twice), an async packed batch with
+    host verdicts collected by sf_sync_packed, then, after a SystemRule is
+    loaded, a sync submit whose rounds take the slot an async batch used last.
+    Every batch's status, wait_ms and rule_idx equal the oracle's, fed the same
+    batches in the same order; twice, so that an engine is destroyed and another created."""
+    w = workloads.config3(R=200, n=12_000, seed=21, split=6)
+    hbs = w["batches"]
+    sysr = [abi.sf_system_rule(highest_system_load=-1, highest_cpu_usage=-1, qps=0.8 * sum(b.n for b in hbs) / 6.0,
+                               avg_rt=-1, max_thread=-1)]
+    ora = so.OracleEngine(w["cfg"])
+    ora.load_flow_rules(w["flow"])
+    want = [ora.submit(hb) for hb in hbs[:5]]
+    ora.load_system_rules(sysr)
+    want.append(ora.submit(hbs[5]))
+    ora.close()
+    st = np.concatenate([v.status for v in want])
+    assert (st == abi.V_PASS).any() and (st == abi.V_BLOCK_FLOW).any(), np.bincount(st)
+    assert (want[5].status == abi.V_BLOCK_SYSTEM).any(), "the SystemRule never fired"
+    for rnd in range(2):
+        e = eng_mod.FlowEngine(w["cfg"])
+        pin = eng_mod.PinnedArrays(e)
+        try:
+            e.load_flow_rules(w["flow"])
+            got = {0: e.submit(hbs[0])}
+            dbs = [eng_mod.DeviceBatch(e, hb) for hb in hbs[1:4]]
+            dvs = [eng_mod.DeviceVerdicts(e, hb.n, with_wait=True, with_rule=True) for hb in hbs[1:4]]
+            for db, dv in zip(dbs, dvs):
+                e.submit_device_async(db, dv)
+            pb = abi.PackedBatch(hbs[4], alloc=pin.array)
+            got[4] = pin.verdicts(hbs[4].n)
+            e.submit_packed_async(pb, got[4])
+            e.sync_packed(got[4])
+            e.load_system_rules(sysr)
+            got[5] = e.submit(hbs[5])
+            e.sync()
+            for k, dv in enumerate(dvs, 1):
+                got[k] = abi.HostVerdicts(hbs[k].n)
+                got[k].status, got[k].wait_ms, got[k].rule_idx = dv.status.numpy(), dv.wait_ms.numpy(), dv.rule_idx.numpy()
+            for k, o in enumerate(want):
+                parity.compare_verdicts(got[k], o, f"round {rnd} batch {k}")
+        finally:
+            pin.free()
+            e.close()
+
+
 def test_async_error_reported_at_sync(eng_mod):
     cfg = abi.default_config(max_resources=8, max_batch=16)
     e = eng_mod.FlowEngine(cfg)
