@@ -329,6 +329,52 @@ typedef struct sf_token_results {
     int32_t* wait_ms;             /* [n] or NULL                               */
 } sf_token_results;
 
+/* ---- cluster concurrency tokens (TokenService.requestConcurrentToken /
+ * releaseConcurrentToken; ConcurrentClusterFlowChecker.java:36-101) -------- */
+#define SF_TOKEN_RELEASE_OK      6
+#define SF_TOKEN_ALREADY_RELEASE 7
+#define SF_CC_ACQUIRE 0
+#define SF_CC_RELEASE 1
+#define SF_CLIENT_NONE 0xFFFFFFFFu        /* null or empty client address */
+/* token id: bits 0..27 pool slot, 28..55 the slot's generation, 56..63
+ * shard_index + 1 (so an id is never 0).  A slot's generation goes up each
+ * time the slot is freed: an id can alias a stale one only after 2^28 reuses
+ * of one slot. */
+#define SF_TOKEN_ID_SHARD(id) ((uint32_t)((uint64_t)(id) >> 56) - 1u)
+
+typedef struct sf_concurrent_config {     /* ClusterFlowConfig, the concurrency fields */
+    int64_t flow_id;
+    int64_t resource_timeout_ms;          /* default 2000 */
+    int64_t client_offline_time_ms;       /* default 2000 */
+} sf_concurrent_config;
+
+typedef struct sf_concurrent_batch {      /* batch order = arrival order; ts_ms non-decreasing */
+    uint32_t n; int32_t mem;              /* SF_MEM_HOST / SF_MEM_DEVICE, as sf_token_batch */
+    const uint8_t*  op;                   /* [n] SF_CC_* */
+    const int64_t*  id;                   /* [n] ACQUIRE: flow id; RELEASE: token id */
+    const int32_t*  count;                /* [n] ACQUIRE: acquireCount (RELEASE: ignored) */
+    const uint32_t* client;               /* [n] ACQUIRE: interned client address */
+    const int64_t*  ts_ms;                /* [n] */
+} sf_concurrent_batch;
+
+typedef struct sf_concurrent_results {
+    int32_t  mem;
+    int8_t*  status;                      /* [n] SF_TOKEN_* */
+    int64_t* token_id;                    /* [n] non-zero only for an OK acquire */
+} sf_concurrent_results;
+
+typedef struct sf_token_node {            /* TokenCacheNode */
+    int64_t  flow_id, client_deadline_ms, resource_deadline_ms;
+    int32_t  count;
+    uint32_t client;
+} sf_token_node;
+
+typedef struct sf_concurrent_stats {
+    uint64_t live_tokens, pool_capacity, pool_grows;
+    uint64_t chunks, chunks_all_pass, rounds;   /* the walk's chunk solver */
+    uint64_t expired;
+} sf_concurrent_stats;
+
 /* ---- state read-back (parity tests, metric snapshot) -------------------- */
 #define SF_WS_ABSENT INT64_MIN    /* bucket slot never created (Java null)     */
 
@@ -550,6 +596,48 @@ int  sf_request_tokens(sf_engine* e, const sf_token_batch* in, sf_token_results*
 int  sf_token_shard(const sf_cluster_flow_rule* flow, uint32_t n_flow, const sf_cluster_param_rule* param,
                     uint32_t n_param, const sf_namespace* ns, uint32_t n_ns, uint32_t shard_count,
                     const int64_t* flow_id, const uint8_t* flags, uint32_t n, uint32_t* out_shard);
+/* Cluster concurrency tokens: the cluster form of THREAD-grade flow control.
+ * sf_request_concurrent decides a batch of acquires and releases as if they
+ * were handed to DefaultTokenService.requestConcurrentToken /
+ * releaseConcurrentToken (DefaultTokenService.java:66-93) one by one in batch
+ * order, against the flow rules of sf_load_cluster_rules:
+ *   acquire  BAD_REQUEST (client SF_CLIENT_NONE, id <= 0 or count <= 0),
+ *            NO_RULE_EXISTS (no cluster flow rule of that id), BLOCKED when
+ *            nowCalls + count (Java int, wrapping) > the threshold (count for
+ *            GLOBAL, count * connected_count otherwise; 0 connections when the
+ *            namespace is not loaded), else OK: nowCalls += count and
+ *            token_id[i] names the stored token.
+ *   release  ALREADY_RELEASE for an id that names no live token (never
+ *            issued, stale generation, slot out of range, 0); NO_RULE_EXISTS
+ *            when the token's rule is no longer loaded (the token stays); else
+ *            RELEASE_OK: the token is removed and nowCalls -= its count.  Of
+ *            several releases of one token in a batch the first is RELEASE_OK.
+ * A release names a token of an earlier call (a client learns the id from the
+ * response).  Sharding follows sf_request_tokens: an acquire belongs to its
+ * rule's owner (sf_token_shard), a release to SF_TOKEN_ID_SHARD(id) (an id
+ * whose shard byte is 0 was issued by no shard: ALREADY_RELEASE anywhere);
+ * another shard's request fails the call with SF_ERR_INVALID and the call
+ * decides nothing (no token issued or removed, nowCalls as before).  shard_count >
+ * 255 is SF_ERR_UNSUPPORTED.  The token pool grows on demand up to 2^28
+ * slots; a batch that could need more is SF_ERR_CAPACITY before any state
+ * changes.  sf_load_cluster_rules keeps nowCalls of a flowId that stays loaded
+ * and drops it otherwise; stored tokens survive a reload
+ * (ClusterFlowRuleManager.java:271-375).
+ * sf_load_concurrent_config replaces the table of time-outs (a flowId not
+ * listed: 2000 / 2000; a value <= 0: SF_ERR_INVALID, FlowRuleUtil.java:195).
+ * sf_concurrent_expire is one run of RegularExpireStrategy.clearToken (:94-136)
+ * at now_ms over every live token; client c is online iff c < n_clients &&
+ * client_online[c] (host memory).  n_expired may be NULL.
+ * sf_concurrent_now is CurrentConcurrencyManager.get (SF_ERR_INVALID: flowId
+ * not loaded); sf_read_token reads a live token (SF_ERR_INVALID: not live). */
+int  sf_load_concurrent_config(sf_engine* e, const sf_concurrent_config* cfg, uint32_t n);
+int  sf_concurrent_reserve(sf_engine* e, uint64_t tokens);
+int  sf_request_concurrent(sf_engine* e, const sf_concurrent_batch* in, sf_concurrent_results* out);
+int  sf_concurrent_expire(sf_engine* e, int64_t now_ms, const uint8_t* client_online, uint32_t n_clients,
+                          uint32_t* n_expired);
+int  sf_concurrent_now(sf_engine* e, int64_t flow_id, int64_t* now_calls);
+int  sf_read_token(sf_engine* e, int64_t token_id, sf_token_node* out);
+int  sf_concurrent_get_stats(sf_engine* e, sf_concurrent_stats* out);
 /* ---- token-server wire path (C1 frames) ------------
  * Replaces the server pipeline of NettyTransportServer.java:84-101 up to the
  * TokenService call and back:

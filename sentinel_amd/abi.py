@@ -560,6 +560,81 @@ class HostTokenResults:
         return r
 
 
+# ---- cluster concurrency tokens (requestConcurrentToken / releaseConcurrentToken)
+TOKEN_OK, TOKEN_BLOCKED, TOKEN_NO_RULE_EXISTS, TOKEN_BAD_REQUEST = 0, 1, 3, -4
+TOKEN_RELEASE_OK = 6
+TOKEN_ALREADY_RELEASE = 7
+CC_ACQUIRE = 0
+CC_RELEASE = 1
+CLIENT_NONE = 0xFFFFFFFF
+
+
+def token_id_shard(token_id: int) -> int:
+    """SF_TOKEN_ID_SHARD: the shard that issued a token id."""
+    return (((int(token_id) & (2 ** 64 - 1)) >> 56) - 1) & 0xFFFFFFFF
+
+
+class sf_concurrent_config(C.Structure):
+    _fields_ = [("flow_id", C.c_int64), ("resource_timeout_ms", C.c_int64), ("client_offline_time_ms", C.c_int64)]
+
+
+class sf_concurrent_batch(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("mem", C.c_int32), ("op", C.c_void_p), ("id", C.c_void_p),
+                ("count", C.c_void_p), ("client", C.c_void_p), ("ts_ms", C.c_void_p)]
+
+
+class sf_concurrent_results(C.Structure):
+    _fields_ = [("mem", C.c_int32), ("status", C.c_void_p), ("token_id", C.c_void_p)]
+
+
+class sf_token_node(C.Structure):
+    _fields_ = [("flow_id", C.c_int64), ("client_deadline_ms", C.c_int64), ("resource_deadline_ms", C.c_int64),
+                ("count", C.c_int32), ("client", C.c_uint32)]
+
+
+class sf_concurrent_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("live_tokens", "pool_capacity", "pool_grows", "chunks",
+                                          "chunks_all_pass", "rounds", "expired")]
+
+
+STRUCT_SIZES.update({n: C.sizeof(c) for n, c in [
+    ("sf_concurrent_config", sf_concurrent_config), ("sf_concurrent_batch", sf_concurrent_batch),
+    ("sf_concurrent_results", sf_concurrent_results), ("sf_token_node", sf_token_node),
+    ("sf_concurrent_stats", sf_concurrent_stats)]})
+
+
+class HostConcurrentBatch:
+    """Acquires (id: flow id) and releases (id: token id) in arrival order."""
+
+    def __init__(self, op, id, count, client, ts_ms):
+        self.op = np.ascontiguousarray(op, np.uint8)
+        self.id = np.ascontiguousarray(id, np.int64)
+        self.count = np.ascontiguousarray(count, np.int32)
+        self.client = np.ascontiguousarray(client, np.uint32)
+        self.ts_ms = np.ascontiguousarray(ts_ms, np.int64)
+        self.n = self.op.shape[0]
+        assert all(a.shape == (self.n,) for a in (self.id, self.count, self.client, self.ts_ms))
+
+    def c_struct(self) -> sf_concurrent_batch:
+        b = sf_concurrent_batch()
+        b.n, b.mem = self.n, MEM_HOST
+        b.op, b.id, b.count, b.client, b.ts_ms = (_ptr(self.op), _ptr(self.id), _ptr(self.count), _ptr(self.client),
+                                                  _ptr(self.ts_ms))
+        return b
+
+
+class HostConcurrentResults:
+    def __init__(self, n: int):
+        self.status = np.full(n, 99, np.int8)
+        self.token_id = np.zeros(n, np.int64)
+
+    def c_struct(self) -> sf_concurrent_results:
+        r = sf_concurrent_results()
+        r.mem = MEM_HOST
+        r.status, r.token_id = _ptr(self.status), _ptr(self.token_id)
+        return r
+
+
 def rules_array(cls, rules):
     arr = (cls * max(1, len(rules)))()
     for i, r in enumerate(rules):

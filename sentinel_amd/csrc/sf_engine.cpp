@@ -20,6 +20,7 @@
 #include "sf_xflow.h"
 #include "sf_sysx.h"
 #include "sf_token.h"
+#include "sf_concur.h"
 #include "sf_wire.h"
 #include "sf_degrade.h"
 #include <rccl/rccl.h>
@@ -41,6 +42,18 @@ static int fail(int code, const std::string& msg) {
             return fail(_e == hipErrorOutOfMemory ? SF_ERR_NOMEM : SF_ERR_DEVICE,       \
                         std::string(#expr ": ") + hipGetErrorString(_e));               \
     } while (0)
+
+// cluster concurrency tokens (sf_concur.hip): the device state with the host's
+// view of it as of the last call
+struct CcHost {
+    CcState cs{};
+    CcWork w{};
+    CcCounters ctr{};                 // device counters after the last call (ctr.top: free slots)
+    uint64_t grows = 0;
+    std::vector<sf_concurrent_config> cfg;    // sf_load_concurrent_config
+    void* stage = nullptr; size_t stage_bytes = 0;
+    uint8_t* online = nullptr; size_t online_bytes = 0;
+};
 
 // a device copy of host event arrays, remembered by their addresses (stage_in_events)
 struct StageBuf {
@@ -134,6 +147,7 @@ struct sf_engine {
     std::vector<sf_hot_item> host_citems;
     std::vector<int64_t> cflow_ids;           // flow rule index -> flowId
     void* tok_stage = nullptr; size_t tok_stage_bytes = 0;
+    CcHost cc;
     int64_t* d_sum = nullptr;
     void* wire_arena = nullptr; size_t wire_bytes = 0;   // sf_serve_frames scratch (grow-only)
     // ENTRY_NODE and the metric snapshot (sf_entry.hip)
@@ -188,6 +202,18 @@ static void free_tok_work(TokWork& w) {
                     w.head, w.head_scan, w.seg_start, w.n_seg, w.sort8_tmp, w.sort64_tmp, w.scan_tmp};
     for (void* p : ptrs) if (p) hipFree(p);
     w = TokWork{};
+}
+
+static void free_cc_work(CcWork& w) {
+    void* ptrs[] = {w.key_in, w.key_out, w.idx_in, w.idx_out, w.delta, w.rslot, w.seg_lo, w.seg_hi, w.sort_tmp};
+    for (void* p : ptrs) if (p) hipFree(p);
+    w = CcWork{};
+}
+static void free_cc(CcHost& c) {
+    free_cc_work(c.w);
+    void* ptrs[] = {c.cs.slots, c.cs.stack, c.cs.claim, c.cs.now, (void*)c.cs.cfg, c.cs.ctr, c.stage, c.online};
+    for (void* p : ptrs) if (p) hipFree(p);
+    c.cs = CcState{};
 }
 
 extern "C" {
@@ -277,6 +303,7 @@ void sf_destroy(sf_engine* e) {
     for (Slot& sl : e->slot) slot_destroy(sl);
     if (e->comm) ncclCommDestroy(e->comm);
     free_tok_work(e->tw);
+    free_cc(e->cc);
     for (auto& x : e->ml_ev) if (x) hipEventDestroy(x);
     for (hipStream_t x : {e->stream, e->stream2, e->stream3, e->stream4, e->sstream}) if (x) hipStreamDestroy(x);
     if (e->enstream && e->en_own) hipStreamDestroy(e->enstream);
@@ -2272,6 +2299,35 @@ static int tok_rebuild(sf_engine* e, bool reset_state) {
     return SF_OK;
 }
 
+// Per-flow-rule tables of the concurrency tokens: the two time-outs (always
+// rebuilt) and nowCalls (replaced by `now` if given, created zeroed if absent).
+static int cc_tables(sf_engine* e, const std::vector<int32_t>* now) {
+    CcState& cs = e->cc.cs;
+    const size_t nf = e->host_cflow.size(), m = std::max<size_t>(nf, 1);
+    std::unordered_map<int64_t, const sf_concurrent_config*> by_id;
+    for (const sf_concurrent_config& c : e->cc.cfg) by_id.emplace(c.flow_id, &c);
+    std::vector<CcCfg> cfg(m, CcCfg{CC_DEFAULT_TIMEOUT, CC_DEFAULT_TIMEOUT});
+    for (size_t i = 0; i < nf; i++) {
+        auto it = by_id.find(e->host_cflow[i].flow_id);
+        if (it != by_id.end()) cfg[i] = CcCfg{it->second->resource_timeout_ms, it->second->client_offline_time_ms};
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (cs.cfg) { hipFree((void*)cs.cfg); cs.cfg = nullptr; }
+    HIP_TRY(hipMalloc((void**)&cs.cfg, m * sizeof(CcCfg)));
+    HIP_TRY(hipMemcpy((void*)cs.cfg, cfg.data(), m * sizeof(CcCfg), hipMemcpyHostToDevice));
+    if (now || !cs.now) {
+        if (cs.now) { hipFree(cs.now); cs.now = nullptr; }
+        HIP_TRY(hipMalloc((void**)&cs.now, m * 4));
+        if (now) HIP_TRY(hipMemcpy(cs.now, now->data(), m * 4, hipMemcpyHostToDevice));
+        else HIP_TRY(hipMemset(cs.now, 0, m * 4));
+    }
+    if (!cs.ctr) {
+        HIP_TRY(hipMalloc((void**)&cs.ctr, sizeof(CcCounters)));
+        HIP_TRY(hipMemset(cs.ctr, 0, sizeof(CcCounters)));
+    }
+    return SF_OK;
+}
+
 int sf_load_namespaces(sf_engine* e, const sf_namespace* ns, uint32_t n) {
     if (!e || (n && !ns)) return fail(SF_ERR_INVALID, "null argument");
     if (n > 255) return fail(SF_ERR_UNSUPPORTED, "at most 255 namespaces");
@@ -2303,10 +2359,26 @@ int sf_load_cluster_rules(sf_engine* e, const sf_cluster_flow_rule* flow, uint32
         if ((uint64_t)param[i].item_offset + param[i].item_count > n_items) return fail(SF_ERR_INVALID, "hot item range");
     }
     std::lock_guard<std::mutex> lk(e->mu);
+    // nowCalls of a flowId that stays loaded is kept (ClusterFlowRuleManager.java:271-375)
+    std::unordered_map<int64_t, int32_t> kept;
+    if (e->cc.cs.now && !e->host_cflow.empty()) {
+        std::vector<int32_t> old(e->host_cflow.size());
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipMemcpy(old.data(), e->cc.cs.now, old.size() * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < old.size(); i++)
+            if (e->host_cflow[i].flow_id > 0) kept.emplace(e->host_cflow[i].flow_id, old[i]);
+    }
     e->host_cflow.assign(flow, flow + n_flow);
     e->host_cparam.assign(param, param + n_param);
     e->host_citems.assign(items, items + n_items);
-    return tok_rebuild(e, true);
+    int rc = tok_rebuild(e, true);
+    if (rc || !e->cc.cs.now) return rc;
+    std::vector<int32_t> now(std::max<uint32_t>(n_flow, 1), 0);
+    for (uint32_t i = 0; i < n_flow; i++) {                    // (the first rule of an id is the one looked up)
+        auto it = kept.find(flow[i].flow_id);
+        if (it != kept.end()) { now[i] = it->second; kept.erase(it); }
+    }
+    return cc_tables(e, &now);
 }
 
 static int tok_work_ensure(sf_engine* e, uint32_t n) {
@@ -2592,6 +2664,211 @@ int sf_cluster_sum(sf_engine* e, int64_t flow_id, int event, int64_t now_ms, int
         HIP_TRY(hipStreamSynchronize(e->stream));
         return SF_OK;
     }
+    return SF_OK;
+}
+
+// ---------------------------------------------------------------- cluster concurrency tokens
+// state of the concurrency tokens present; caller holds e->mu
+static int cc_ready(sf_engine* e) {
+    { int r2 = tok_ready(e); if (r2) return r2; }
+    if (!e->cc.cs.now || !e->cc.cs.cfg || !e->cc.cs.ctr) return cc_tables(e, nullptr);
+    return SF_OK;
+}
+
+static int cc_read_counters(sf_engine* e) {
+    HIP_TRY(hipMemcpyAsync(&e->cc.ctr, e->cc.cs.ctr, sizeof(CcCounters), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SF_OK;
+}
+
+// The pool holds at least `min_cap` slots and at least `need_free` free ones:
+// a larger array with the old one copied and the new slots pushed, so slot
+// numbers and live ids stay valid.  SF_ERR_CAPACITY past 2^28 slots, nothing changed.
+static int cc_pool_ensure(sf_engine* e, uint64_t need_free, uint64_t min_cap) {
+    CcHost& c = e->cc;
+    CcState& cs = c.cs;
+    const uint64_t cap = cs.cap, free_now = c.ctr.top;
+    if (free_now >= need_free && cap >= min_cap && cap) return SF_OK;
+    uint64_t ncap = std::max<uint64_t>(min_cap, cap);
+    if (free_now < need_free) ncap = std::max<uint64_t>({ncap, cap + (need_free - free_now), 2 * cap});
+    if (!cap && !min_cap) ncap = std::max<uint64_t>(ncap, 1024);
+    ncap = std::max<uint64_t>(ncap, 1);
+    if (ncap > CC_MAX_SLOTS) ncap = CC_MAX_SLOTS;
+    if (ncap < min_cap || ncap - cap + free_now < need_free)
+        return fail(SF_ERR_CAPACITY, "concurrency token pool: more than 2^28 slots needed");
+    if (ncap == cap) return SF_OK;
+    hipStream_t s = e->stream;
+    CcSlot* slots = nullptr; uint32_t* stack = nullptr; uint32_t* claim = nullptr;
+    hipError_t he = hipMalloc((void**)&slots, ncap * sizeof(CcSlot));
+    if (he == hipSuccess) he = hipMalloc((void**)&stack, ncap * 4);
+    if (he == hipSuccess) he = hipMalloc((void**)&claim, ncap * 4);
+    if (he != hipSuccess) {
+        for (void* p : {(void*)slots, (void*)stack, (void*)claim}) if (p) hipFree(p);
+        return fail(SF_ERR_NOMEM, std::string("concurrency token pool: ") + hipGetErrorString(he));
+    }
+    HIP_TRY(hipMemsetAsync(slots, 0, ncap * sizeof(CcSlot), s));
+    if (cap) {
+        HIP_TRY(hipMemcpyAsync(slots, cs.slots, cap * sizeof(CcSlot), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(stack, cs.stack, cap * 4, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(claim, cs.claim, cap * 4, hipMemcpyDeviceToDevice, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    for (void* p : {(void*)cs.slots, (void*)cs.stack, (void*)cs.claim}) if (p) hipFree(p);
+    cs.slots = slots; cs.stack = stack; cs.claim = claim; cs.cap = (uint32_t)ncap;
+    HIP_TRY(cc_push_range(cs, (uint32_t)cap, (uint32_t)ncap, s));
+    if (cap) c.grows++;
+    return cc_read_counters(e);
+}
+
+static int cc_work_ensure(sf_engine* e, uint32_t n) {
+    CcWork& w = e->cc.w;
+    const uint32_t nf = (uint32_t)e->host_cflow.size();
+    if (n <= w.cap && nf <= w.nf_cap) return SF_OK;
+    const size_t N = std::max<uint32_t>(n, w.cap), F = std::max<uint32_t>({nf, w.nf_cap, 1u});
+    free_cc_work(w);
+    auto A = [&](void** p, size_t bytes) -> int { return hipMalloc(p, std::max<size_t>(bytes, 16)) != hipSuccess; };
+    int rc = 0;
+    rc |= A((void**)&w.key_in, N * 4); rc |= A((void**)&w.key_out, N * 4);
+    rc |= A((void**)&w.idx_in, N * 4); rc |= A((void**)&w.idx_out, N * 4);
+    rc |= A((void**)&w.delta, N * 4); rc |= A((void**)&w.rslot, N * 4);
+    rc |= A((void**)&w.seg_lo, F * 4); rc |= A((void**)&w.seg_hi, F * 4);
+    if (rc) return fail(SF_ERR_NOMEM, "concurrency work buffers");
+    HIP_TRY(cc_query_temp((uint32_t)N, &w.sort_bytes));
+    if (A(&w.sort_tmp, w.sort_bytes)) return fail(SF_ERR_NOMEM, "concurrency work buffers");
+    w.cap = (uint32_t)N; w.nf_cap = (uint32_t)F;
+    return SF_OK;
+}
+
+int sf_load_concurrent_config(sf_engine* e, const sf_concurrent_config* cfg, uint32_t n) {
+    if (!e || (n && !cfg)) return fail(SF_ERR_INVALID, "null argument");
+    for (uint32_t i = 0; i < n; i++)
+        if (cfg[i].resource_timeout_ms <= 0 || cfg[i].client_offline_time_ms <= 0)      // FlowRuleUtil.java:195
+            return fail(SF_ERR_INVALID, "concurrent config: time-outs must be > 0");
+    std::lock_guard<std::mutex> lk(e->mu);
+    e->cc.cfg.assign(cfg, cfg + n);
+    return e->cc.cs.cfg ? cc_tables(e, nullptr) : SF_OK;
+}
+
+int sf_concurrent_reserve(sf_engine* e, uint64_t tokens) {
+    if (!e) return fail(SF_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    { int r2 = cc_ready(e); if (r2) return r2; }
+    return cc_pool_ensure(e, 0, std::max<uint64_t>(tokens, 1));
+}
+
+int sf_request_concurrent(sf_engine* e, const sf_concurrent_batch* in, sf_concurrent_results* out) {
+    if (!e || !in || !out || !out->status || !out->token_id) return fail(SF_ERR_INVALID, "null argument");
+    if (in->n == 0) return SF_OK;
+    if (!in->op || !in->id || !in->count || !in->client || !in->ts_ms) return fail(SF_ERR_INVALID, "missing request array");
+    if (e->cfg.shard_count > 255) return fail(SF_ERR_UNSUPPORTED, "concurrency tokens: at most 255 shards (token id layout)");
+    std::lock_guard<std::mutex> lk(e->mu);
+    const uint32_t n = in->n;
+    { int r2 = cc_ready(e); if (r2) return r2; }
+    { int r2 = cc_work_ensure(e, n); if (r2) return r2; }
+    { int r2 = cc_pool_ensure(e, n, 0); if (r2) return r2; }     // a slot for every request, before any state changes
+    CcHost& c = e->cc;
+    hipStream_t s = e->stream;
+    const size_t off_op = 0, off_id = align_up(off_op + n), off_cnt = align_up(off_id + (size_t)n * 8),
+                 off_cl = align_up(off_cnt + (size_t)n * 4), off_ts = align_up(off_cl + (size_t)n * 4),
+                 off_st = align_up(off_ts + (size_t)n * 8), off_tid = align_up(off_st + n),
+                 need = align_up(off_tid + (size_t)n * 8);
+    if (need > c.stage_bytes) {
+        if (c.stage) hipFree(c.stage);
+        c.stage = nullptr; c.stage_bytes = 0;
+        HIP_TRY(hipMalloc(&c.stage, need));
+        c.stage_bytes = need;
+    }
+    char* base = (char*)c.stage;
+    CcBatch b{};
+    b.n = n;
+    if (in->mem == SF_MEM_HOST) {
+        HIP_TRY(hipMemcpyAsync(base + off_op, in->op, n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(base + off_id, in->id, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(base + off_cnt, in->count, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(base + off_cl, in->client, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(base + off_ts, in->ts_ms, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        b.op = (const uint8_t*)(base + off_op); b.id = (const int64_t*)(base + off_id);
+        b.count = (const int32_t*)(base + off_cnt); b.client = (const uint32_t*)(base + off_cl);
+        b.ts = (const int64_t*)(base + off_ts);
+    } else {
+        b.op = in->op; b.id = in->id; b.count = in->count; b.client = in->client; b.ts = in->ts_ms;
+    }
+    const bool host_out = out->mem == SF_MEM_HOST;
+    CcOut o{host_out ? (int8_t*)(base + off_st) : out->status, host_out ? (int64_t*)(base + off_tid) : out->token_id};
+    HIP_TRY(hipMemsetAsync(e->st.err, 0, sizeof(int32_t), s));
+    hipError_t le = cc_launch(e->ts, c.cs, c.w, b, o, s);
+    if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("concurrent launch: ") + hipGetErrorString(le));
+    if (host_out) {
+        HIP_TRY(hipMemcpyAsync(out->status, o.status, n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out->token_id, o.token_id, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    }
+    int32_t err = 0;
+    HIP_TRY(hipMemcpyAsync(&err, e->st.err, 4, hipMemcpyDeviceToHost, s));
+    { int r2 = cc_read_counters(e); if (r2) return r2; }
+    if (err) return fail(err, err == SF_ERR_CAPACITY ? "concurrency token pool exhausted"
+                                                     : "invalid concurrent batch (a request owned by another shard?)");
+    return SF_OK;
+}
+
+int sf_concurrent_expire(sf_engine* e, int64_t now_ms, const uint8_t* client_online, uint32_t n_clients,
+                         uint32_t* n_expired) {
+    if (!e || (n_clients && !client_online)) return fail(SF_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    { int r2 = cc_ready(e); if (r2) return r2; }
+    CcHost& c = e->cc;
+    if (n_clients > c.online_bytes) {
+        if (c.online) hipFree(c.online);
+        c.online = nullptr; c.online_bytes = 0;
+        HIP_TRY(hipMalloc((void**)&c.online, n_clients));
+        c.online_bytes = n_clients;
+    }
+    if (n_clients) HIP_TRY(hipMemcpyAsync(c.online, client_online, n_clients, hipMemcpyHostToDevice, e->stream));
+    const uint64_t before = c.ctr.expired;
+    HIP_TRY(cc_expire(e->ts, c.cs, now_ms, c.online, n_clients, e->stream));
+    { int r2 = cc_read_counters(e); if (r2) return r2; }
+    if (n_expired) *n_expired = (uint32_t)(c.ctr.expired - before);
+    return SF_OK;
+}
+
+int sf_concurrent_now(sf_engine* e, int64_t flow_id, int64_t* now_calls) {
+    if (!e || !now_calls) return fail(SF_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (flow_id > 0)
+        for (size_t i = 0; i < e->host_cflow.size(); i++) {
+            if (e->host_cflow[i].flow_id != flow_id) continue;
+            { int r2 = cc_ready(e); if (r2) return r2; }
+            int32_t v = 0;
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            HIP_TRY(hipMemcpy(&v, e->cc.cs.now + i, 4, hipMemcpyDeviceToHost));
+            *now_calls = v;
+            return SF_OK;
+        }
+    return fail(SF_ERR_INVALID, "sf_concurrent_now: flowId not loaded");
+}
+
+int sf_read_token(sf_engine* e, int64_t token_id, sf_token_node* out) {
+    if (!e || !out) return fail(SF_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    const uint64_t tid = (uint64_t)token_id;
+    const uint32_t slot = (uint32_t)tid & CC_SLOT_MASK, gen = (uint32_t)(tid >> CC_SLOT_BITS) & CC_SLOT_MASK;
+    if ((tid >> 56) != (uint64_t)e->cfg.shard_index + 1 || slot >= e->cc.cs.cap)
+        return fail(SF_ERR_INVALID, "sf_read_token: not a live token");
+    CcSlot sl;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(&sl, e->cc.cs.slots + slot, sizeof sl, hipMemcpyDeviceToHost));
+    if (!sl.live || sl.gen != gen) return fail(SF_ERR_INVALID, "sf_read_token: not a live token");
+    out->flow_id = sl.flow_id; out->client_deadline_ms = sl.client_deadline; out->resource_deadline_ms = sl.resource_deadline;
+    out->count = sl.count; out->client = sl.client;
+    return SF_OK;
+}
+
+int sf_concurrent_get_stats(sf_engine* e, sf_concurrent_stats* out) {
+    if (!e || !out) return fail(SF_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    const CcHost& c = e->cc;
+    out->live_tokens = (uint64_t)c.cs.cap - c.ctr.top; out->pool_capacity = c.cs.cap; out->pool_grows = c.grows;
+    out->chunks = c.ctr.chunks; out->chunks_all_pass = c.ctr.chunks_all_pass; out->rounds = c.ctr.rounds;
+    out->expired = c.ctr.expired;
     return SF_OK;
 }
 

@@ -20,6 +20,7 @@
 //   ns / lim [n_ns]             namespace table and its RequestLimiter (UnaryLeapArray(10, 1000))
 //   cptab   open-addressed      (param rule, value) -> per-value window counts
 #pragma once
+#include "sf_decide.h"
 #include "sf_internal.h"
 
 namespace sf {
@@ -67,6 +68,21 @@ struct TokState {
     uint8_t* rmulti;             // [n_rules] per call: a param rule with a multi-value request (serial group)
     uint32_t shard_count, shard_index;
 };
+
+#if defined(__HIPCC__)
+// flowId -> rule index of the flow (or param) rule table, -1: none (shared with sf_concur.hip)
+__device__ __forceinline__ uint64_t id_hash(int64_t id) { return mix64((uint64_t)id * 0x9e3779b97f4a7c15ULL); }
+__device__ __forceinline__ int32_t id_lookup(const TokState& ts, int64_t id, bool param) {
+    uint64_t i = id_hash(id) & ts.id_mask;
+    for (uint64_t p = 0; p <= ts.id_mask; p++) {
+        const IdSlot& s = ts.idtab[i];
+        if (s.id == 0) return -1;
+        if (s.id == id) return param ? s.param : s.flow;
+        i = (i + 1) & ts.id_mask;
+    }
+    return -1;
+}
+#endif
 
 struct TokBatch {
     uint32_t n;

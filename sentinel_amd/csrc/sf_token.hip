@@ -40,19 +40,6 @@ constexpr int8_t TOK_PENDING = 100;
 
 static inline unsigned tblocks(size_t n, unsigned t) { return (unsigned)((n + t - 1) / t); }
 
-__device__ __forceinline__ uint64_t id_hash(int64_t id) { return mix64((uint64_t)id * 0x9e3779b97f4a7c15ULL); }
-
-__device__ int32_t id_lookup(const TokState& ts, int64_t id, bool param) {
-    uint64_t i = id_hash(id) & ts.id_mask;
-    for (uint64_t p = 0; p <= ts.id_mask; p++) {
-        const IdSlot& s = ts.idtab[i];
-        if (s.id == 0) return -1;
-        if (s.id == id) return param ? s.param : s.flow;
-        i = (i + 1) & ts.id_mask;
-    }
-    return -1;
-}
-
 // DefaultTokenService.requestToken / requestParamToken up to the checker
 __global__ void k_tok_prep(TokState ts, TokBatch b, TokWork w, TokOut out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -76,6 +76,13 @@ def _declare(L):
     f("sf_load_cluster_rules", I, P, C.POINTER(abi.sf_cluster_flow_rule), U32,
       C.POINTER(abi.sf_cluster_param_rule), U32, C.POINTER(abi.sf_hot_item), U32)
     f("sf_request_tokens", I, P, C.POINTER(abi.sf_token_batch), C.POINTER(abi.sf_token_results))
+    f("sf_load_concurrent_config", I, P, C.POINTER(abi.sf_concurrent_config), U32)
+    f("sf_concurrent_reserve", I, P, C.c_uint64)
+    f("sf_request_concurrent", I, P, C.POINTER(abi.sf_concurrent_batch), C.POINTER(abi.sf_concurrent_results))
+    f("sf_concurrent_expire", I, P, C.c_int64, P, U32, C.POINTER(U32))
+    f("sf_concurrent_now", I, P, C.c_int64, C.POINTER(C.c_int64))
+    f("sf_read_token", I, P, C.c_int64, C.POINTER(abi.sf_token_node))
+    f("sf_concurrent_get_stats", I, P, C.POINTER(abi.sf_concurrent_stats))
     f("sf_serve_frames", I, P, C.POINTER(abi.sf_wire_batch), C.POINTER(abi.sf_wire_out))
     f("sf_string_key", C.c_uint64, C.c_char_p, C.c_uint32)
     f("sf_cluster_sum", I, P, C.c_int64, I, C.c_int64, C.POINTER(C.c_int64))
@@ -630,6 +637,44 @@ class FlowEngine:
         r = out.c_struct()
         _check(lib().sf_request_tokens(self.h, C.byref(b), C.byref(r)))
         return out
+
+    # ---- cluster concurrency tokens (TokenService.requestConcurrentToken / releaseConcurrentToken)
+    def load_concurrent_config(self, cfg=()):
+        """(flow_id, resource_timeout_ms, client_offline_time_ms) triples or sf_concurrent_config."""
+        rows = [c if isinstance(c, abi.sf_concurrent_config) else abi.sf_concurrent_config(*c) for c in cfg]
+        _check(lib().sf_load_concurrent_config(self.h, abi.rules_array(abi.sf_concurrent_config, rows), len(rows)))
+
+    def concurrent_reserve(self, tokens: int):
+        _check(lib().sf_concurrent_reserve(self.h, tokens))
+
+    def request_concurrent(self, batch: abi.HostConcurrentBatch) -> abi.HostConcurrentResults:
+        out = abi.HostConcurrentResults(batch.n)
+        b = batch.c_struct()
+        r = out.c_struct()
+        _check(lib().sf_request_concurrent(self.h, C.byref(b), C.byref(r)))
+        return out
+
+    def concurrent_expire(self, now_ms, client_online=()) -> int:
+        """One RegularExpireStrategy sweep at now_ms; client c is online iff client_online[c]."""
+        on = np.ascontiguousarray(client_online, np.uint8)
+        n = C.c_uint32()
+        _check(lib().sf_concurrent_expire(self.h, now_ms, abi._ptr(on) if on.size else None, on.size, C.byref(n)))
+        return n.value
+
+    def concurrent_now(self, flow_id) -> int:
+        v = C.c_int64()
+        _check(lib().sf_concurrent_now(self.h, flow_id, C.byref(v)))
+        return v.value
+
+    def read_token(self, token_id) -> abi.sf_token_node:
+        t = abi.sf_token_node()
+        _check(lib().sf_read_token(self.h, int(token_id), C.byref(t)))
+        return t
+
+    def concurrent_stats(self) -> abi.sf_concurrent_stats:
+        s = abi.sf_concurrent_stats()
+        _check(lib().sf_concurrent_get_stats(self.h, C.byref(s)))
+        return s
 
     def serve_frames(self, streams, now_ms) -> abi.WireResult:
         """Inbound C1 bytes of each connection -> response frames (sf_serve_frames)."""
