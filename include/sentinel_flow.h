@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 1
+#define SF_ABI_VERSION 2
 
 /* ---- return codes ------------------------------------------------------ */
 #define SF_OK               0
@@ -492,7 +492,38 @@ int  sf_submit_async(sf_engine* e, const sf_event_batch* in, sf_verdicts* out);
  *   non-decreasing, ms_end[n_ms - 1] == n; else SF_ERR_INVALID at sync), so
  *   event i is at ts_base + the first m with ms_end[m] > i.  n_ms <= 2^20.
  * A config-3 batch (2^27 events over 4 s) crosses PCIe in 0.63 GB instead of
- * 1.16 GB.                                                                 */
+ * 1.16 GB.
+ *
+ * ParamFlow arguments and context names (both forms).  The meaning is the SoA
+ * form's: the batch is decided exactly as sf_submit decides an sf_event_batch
+ * with this arg_slots, n_args[i] = the number of values listed for event i
+ * (0 when the event is not listed), the same values in slot order, the same
+ * elements and the same contexts.  An EXIT carries its entry's arguments and
+ * context, as there.  A batch with the whole tail zero has neither.
+ *   arg_event[j], strictly increasing and < n, is the index of the j-th event
+ *     that carries arguments (j < n_arg_events).  NULL: n_arg_events == n and
+ *     event j is j.
+ *   arg_off: event arg_event[j] carries the values [arg_off[j], arg_off[j+1])
+ *     in slot order, at most arg_slots (1..SF_MAX_ARGS) of them; the table is
+ *     non-decreasing and arg_off[n_arg_events] == n_values.  NULL: exactly
+ *     arg_slots values per listed event, value (j, s) at j*arg_slots + s.
+ *   arg_tag / arg_bits [n_values]: typed as in sf_event_batch.
+ *   elem_off [n_values + 1]: the value v whose tag is SF_TAG_COLLECTION has the
+ *     elements elem_tag / elem_bits[elem_off[v] .. elem_off[v+1]); non-decreasing,
+ *     elem_off[n_values] == n_elems.  NULL only when no value is a collection.
+ *   context [n] or NULL, as in sf_event_batch.
+ * Inbound bytes per event of the two shortcuts: a batch whose events all carry
+ * exactly arg_slots values (arg_event and arg_off NULL) adds 9 B per slot and
+ * nothing else -- 13 B per event narrow with one argument, against the SoA
+ * form's 26 (17 + 9); with the explicit lists an event without arguments adds
+ * nothing and a listed one 8 B (its index and offset) + 9 B per value.
+ * A malformed table (an index >= n, arg_event not increasing, arg_off
+ * decreasing, spanning more than arg_slots or not ending at n_values, elem_off
+ * decreasing or not ending at n_elems, a collection without elem_off) is
+ * SF_ERR_INVALID, reported like a short exit_ref array: by the call when
+ * synchronous, by the batch's own sync when asynchronous.  The whole table is
+ * checked before any of it is used: the engine reads nothing through a bad
+ * index, and no event of a refused table is given arguments.                */
 #define SF_PK_COUNT_SHIFT 52
 #define SF_PK_FLAGS_SHIFT 59
 #define SF_PK4_COUNT_SHIFT 24
@@ -513,6 +544,19 @@ typedef struct sf_packed_batch {
     const uint32_t* ms_end;       /* [n_ms]: the narrow form's time table       */
     uint32_t        n_ms;
     uint32_t        pad0;
+    /* ParamFlow arguments, collection elements and contexts (above)          */
+    uint32_t        n_arg_events;
+    uint32_t        n_values;
+    uint32_t        arg_slots;    /* 1..SF_MAX_ARGS when n_arg_events != 0      */
+    uint32_t        n_elems;
+    const uint32_t* arg_event;    /* [n_arg_events] or NULL (every event)       */
+    const uint32_t* arg_off;      /* [n_arg_events + 1] or NULL (arg_slots each) */
+    const uint8_t*  arg_tag;      /* [n_values]                                 */
+    const uint64_t* arg_bits;     /* [n_values]                                 */
+    const uint32_t* elem_off;     /* [n_values + 1] or NULL (no collection)     */
+    const uint8_t*  elem_tag;     /* [n_elems]                                  */
+    const uint64_t* elem_bits;    /* [n_elems]                                  */
+    const uint32_t* context;      /* [n] or NULL                                */
 } sf_packed_batch;
 int  sf_submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* out);
 /* Enqueued only; sf_sync waits and reports the first error.  Host arrays

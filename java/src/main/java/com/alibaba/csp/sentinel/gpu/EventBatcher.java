@@ -24,11 +24,16 @@ import static java.lang.foreign.ValueLayout.JAVA_SHORT;
  * TimeUtil.currentTimeMillis() taken at enqueue and made non-decreasing in
  * queue order, as the engine requires.  The arrays are page-locked host
  * memory from sf_host_alloc (the engine's H2D copy runs at PCIe speed, no
- * staging copy); a batch without ParamFlow arguments or context names, whose
- * clock spans less than 2^20 ms, goes as sf_packed_batch -- in the narrow form
- * (4 bytes per event plus a table of the batch's milliseconds) when every
- * resource id is below 2^24, else 8 bytes per event --, every other one as
- * the sf_event_batch SoA (sf_submit).
+ * staging copy); a batch whose clock spans less than 2^20 ms goes as
+ * sf_packed_batch -- in the narrow form (4 bytes per event plus a table of the
+ * batch's milliseconds) when every resource id is below 2^24, else 8 bytes per
+ * event.  ParamFlow arguments travel with it as the explicit lists of the
+ * packed form: only the events that have arguments are listed (their index,
+ * the range of their values, at most ARG_SLOTS typed values each, packed by
+ * ParamPacker as on the SoA path, and the elements of Collection / array
+ * values in a CSR indexed by value); context names as one id per event, sent
+ * only when some event has a non-default context.  A batch that spans 2^20 ms
+ * or more goes as the sf_event_batch SoA (sf_submit).
  *
  * Latency / throughput contract.  Packed batches are double-buffered: the
  * flusher enqueues batch k+1 with sf_submit_packed_sparse_async into the
@@ -71,6 +76,13 @@ final class EventBatcher implements Runnable {
         // the narrow form: 4-byte words and ms_end, the events up to each millisecond of the batch
         final MemorySegment pev4 = pinned(4L * maxBatch), pms = pinned(4L * PK4_MAX_MS);
         final MemorySegment pcext = pinned(4L * maxBatch), porigin = pinned(4L * maxBatch);
+        // ParamFlow arguments as lists (arg_event / arg_off: the events with arguments and their
+        // value ranges), the collections' elements (a CSR over the values) and the context ids
+        final MemorySegment pargEvent = pinned(4L * maxBatch), pargOff = pinned(4L * (maxBatch + 1L));
+        final MemorySegment pargTag = pinned((long) ARG_SLOTS * maxBatch), pargBits = pinned(8L * ARG_SLOTS * maxBatch);
+        final MemorySegment pelemOff = pinned(4L * ((long) ARG_SLOTS * maxBatch + 1));
+        final MemorySegment pelemTag = pinned(MAX_ELEMS), pelemBits = pinned(8L * MAX_ELEMS);
+        final MemorySegment pcontext = pinned(4L * maxBatch);
         // verdicts copied back sparse: a status byte per event, the nonzero waits / rule
         // indices as (index << 32 | value) lists, maxBatch / 64 of each with the batch
         final MemorySegment pstatus = pinned(maxBatch), pwaits = pinned(8L * maxBatch), prules = pinned(8L * maxBatch);
@@ -286,22 +298,55 @@ final class EventBatcher implements Runnable {
     }
 
     /**
-     * The batch as sf_packed_batch when it fits (no arguments, no context
-     * names, clock span < 2^20 ms): enqueued into the free buffer set, then the
-     * batch before it collected; false: the caller builds the SoA batch.
+     * The batch as sf_packed_batch when it fits (clock span < 2^20 ms, at most
+     * MAX_ELEMS collection elements), with its arguments, elements and context
+     * ids: enqueued into the free buffer set, then the batch before it
+     * collected; false: the caller builds the SoA batch.
      */
     private boolean flushPacked(List<Ticket> b, long bs) throws Throwable {
         final int n = b.size();
         long t0 = Long.MIN_VALUE, last = lastTs;
         boolean narrow = true;
         for (Ticket t : b) {
-            if ((t.args != null && t.args.length > 0) || t.context != 0) return false;
             last = Math.max(last, t.ts);
             if (t0 == Long.MIN_VALUE) t0 = last;
             narrow &= (t.resource & 0xffffffffL) < (1L << 24);
         }
         if (last - t0 >= (1L << 20)) return false;
         final PackedBuf p = pbufs[pcur];             // not the in-flight set: sets alternate
+        // the arguments first (nothing of the batch is committed yet): event i is listed when it
+        // has at least one argument; value v of the batch is its next slot, ARG_SLOTS at most
+        int nae = 0, nv = 0, ne = 0;
+        boolean anyContext = false, anyColl = false;
+        p.pargOff.setAtIndex(JAVA_INT, 0, 0);
+        p.pelemOff.setAtIndex(JAVA_INT, 0, 0);
+        for (int i = 0; i < n; i++) {
+            Ticket t = b.get(i);
+            p.pcontext.setAtIndex(JAVA_INT, i, t.context);
+            anyContext |= t.context != 0;
+            final int na = t.args == null ? 0 : Math.min(t.args.length, ARG_SLOTS);
+            if (na == 0) continue;
+            p.pargEvent.setAtIndex(JAVA_INT, nae, i);
+            for (int s = 0; s < na; s++) {
+                Object v = ParamPacker.key(t.args[s]);
+                byte tag = ParamPacker.tag(v);
+                p.pargTag.setAtIndex(JAVA_BYTE, nv, tag);
+                p.pargBits.setAtIndex(JAVA_LONG, nv, tag == TAG_COLLECTION ? 0L : ParamPacker.bits(v));
+                if (tag == TAG_COLLECTION) {
+                    anyColl = true;
+                    for (Object el : ParamPacker.elements(v)) {
+                        if (ne >= MAX_ELEMS) return false;   // (the SoA path reports it as before)
+                        p.pelemTag.setAtIndex(JAVA_BYTE, ne, ParamPacker.tag(el));
+                        p.pelemBits.setAtIndex(JAVA_LONG, ne, ParamPacker.bits(el));
+                        ne++;
+                    }
+                }
+                nv++;
+                p.pelemOff.setAtIndex(JAVA_INT, nv, ne);
+            }
+            nae++;
+            p.pargOff.setAtIndex(JAVA_INT, nae, nv);
+        }
         int nx = 0, nc = 0, ms = 0;
         boolean anyOrigin = false;
         for (int i = 0; i < n; i++) {
@@ -347,6 +392,19 @@ final class EventBatcher implements Runnable {
         pk.set(ADDRESS, off(PACKED_BATCH, "origin"), anyOrigin ? p.porigin : MemorySegment.NULL);
         pk.set(JAVA_INT, off(PACKED_BATCH, "n_exit"), nx);
         pk.set(JAVA_INT, off(PACKED_BATCH, "n_count_ext"), nc);
+        // the explicit lists; no event with arguments: a zeroed tail
+        pk.set(JAVA_INT, off(PACKED_BATCH, "n_arg_events"), nae);
+        pk.set(JAVA_INT, off(PACKED_BATCH, "n_values"), nv);
+        pk.set(JAVA_INT, off(PACKED_BATCH, "arg_slots"), nae > 0 ? ARG_SLOTS : 0);
+        pk.set(JAVA_INT, off(PACKED_BATCH, "n_elems"), anyColl ? ne : 0);
+        pk.set(ADDRESS, off(PACKED_BATCH, "arg_event"), nae > 0 ? p.pargEvent : MemorySegment.NULL);
+        pk.set(ADDRESS, off(PACKED_BATCH, "arg_off"), nae > 0 ? p.pargOff : MemorySegment.NULL);
+        pk.set(ADDRESS, off(PACKED_BATCH, "arg_tag"), nv > 0 ? p.pargTag : MemorySegment.NULL);
+        pk.set(ADDRESS, off(PACKED_BATCH, "arg_bits"), nv > 0 ? p.pargBits : MemorySegment.NULL);
+        pk.set(ADDRESS, off(PACKED_BATCH, "elem_off"), anyColl ? p.pelemOff : MemorySegment.NULL);
+        pk.set(ADDRESS, off(PACKED_BATCH, "elem_tag"), anyColl ? p.pelemTag : MemorySegment.NULL);
+        pk.set(ADDRESS, off(PACKED_BATCH, "elem_bits"), anyColl ? p.pelemBits : MemorySegment.NULL);
+        pk.set(ADDRESS, off(PACKED_BATCH, "context"), anyContext ? p.pcontext : MemorySegment.NULL);
         MemorySegment v = p.pverdicts;
         v.set(ADDRESS, off(SPARSE_VERDICTS, "status"), p.pstatus);
         v.set(ADDRESS, off(SPARSE_VERDICTS, "waits"), p.pwaits);

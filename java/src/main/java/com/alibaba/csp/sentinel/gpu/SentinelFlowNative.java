@@ -129,14 +129,22 @@ final class SentinelFlowNative {
             ADDRESS.withName("origin"), ADDRESS.withName("context"));
 
     /** sf_packed_batch: 8 bytes per event (res | ts - ts_base << 32 | count << 52 | flags << 59); the
-     *  narrow form (ev NULL): ev4 words res | count << 24 | flags << 27 and the table ms_end[n_ms]. */
+     *  narrow form (ev NULL): ev4 words res | count << 24 | flags << 27 and the table ms_end[n_ms].
+     *  The tail carries ParamFlow arguments as lists (the events with arguments, their value ranges,
+     *  the typed values, the collections' element CSR indexed by value) and the context ids. */
     static final StructLayout PACKED_BATCH = MemoryLayout.structLayout(
             JAVA_INT.withName("n"), JAVA_INT.withName("mem"), JAVA_LONG.withName("ts_base"),
             ADDRESS.withName("ev"), ADDRESS.withName("exit_ref"), ADDRESS.withName("exit_cts"),
             ADDRESS.withName("count_ext"), ADDRESS.withName("origin"),
             JAVA_INT.withName("n_exit"), JAVA_INT.withName("n_count_ext"),
             ADDRESS.withName("ev4"), ADDRESS.withName("ms_end"), JAVA_INT.withName("n_ms"),
-            JAVA_INT.withName("pad0"));
+            JAVA_INT.withName("pad0"),
+            JAVA_INT.withName("n_arg_events"), JAVA_INT.withName("n_values"),
+            JAVA_INT.withName("arg_slots"), JAVA_INT.withName("n_elems"),
+            ADDRESS.withName("arg_event"), ADDRESS.withName("arg_off"),
+            ADDRESS.withName("arg_tag"), ADDRESS.withName("arg_bits"),
+            ADDRESS.withName("elem_off"), ADDRESS.withName("elem_tag"), ADDRESS.withName("elem_bits"),
+            ADDRESS.withName("context"));
     static final int PK_COUNT_SHIFT = 52, PK_FLAGS_SHIFT = 59;
     static final int PK4_COUNT_SHIFT = 24, PK4_FLAGS_SHIFT = 27, PK4_MAX_MS = 1048576;
 

@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-SF_ABI_VERSION = 1
+SF_ABI_VERSION = 2
 
 SF_OK = 0
 SF_ERR_INVALID = -1
@@ -274,7 +274,11 @@ class sf_packed_batch(C.Structure):
     _fields_ = [("n", C.c_uint32), ("mem", C.c_int32), ("ts_base", C.c_int64), ("ev", C.c_void_p),
                 ("exit_ref", C.c_void_p), ("exit_cts", C.c_void_p), ("count_ext", C.c_void_p),
                 ("origin", C.c_void_p), ("n_exit", C.c_uint32), ("n_count_ext", C.c_uint32),
-                ("ev4", C.c_void_p), ("ms_end", C.c_void_p), ("n_ms", C.c_uint32), ("pad0", C.c_uint32)]
+                ("ev4", C.c_void_p), ("ms_end", C.c_void_p), ("n_ms", C.c_uint32), ("pad0", C.c_uint32),
+                ("n_arg_events", C.c_uint32), ("n_values", C.c_uint32), ("arg_slots", C.c_uint32),
+                ("n_elems", C.c_uint32), ("arg_event", C.c_void_p), ("arg_off", C.c_void_p),
+                ("arg_tag", C.c_void_p), ("arg_bits", C.c_void_p), ("elem_off", C.c_void_p),
+                ("elem_tag", C.c_void_p), ("elem_bits", C.c_void_p), ("context", C.c_void_p)]
 
 
 STRUCT_SIZES["sf_packed_batch"] = C.sizeof(sf_packed_batch)
@@ -285,7 +289,12 @@ class PackedBatch:
     resource | ts - ts_base << 32 | acquireCount << 52 | flags << 59, plus the
     EXIT events' entry_ref / create_ts and the acquireCounts outside 1..127 as
     sparse arrays).  ``alloc`` places the arrays (np.empty by default; a
-    PinnedArrays.array for page-locked memory)."""
+    PinnedArrays.array for page-locked memory).
+
+    ParamFlow arguments, collection elements and contexts of ``hb`` travel
+    with it: when every event has exactly arg_slots values, as the values
+    alone (arg_event and arg_off None: 9 bytes per slot and event); otherwise
+    as the explicit lists, which hold only the events with n_args > 0."""
 
     def __init__(self, hb: "HostBatch", alloc=None, narrow=False):
         """narrow: the 4-byte form (resource ids below 2^24; acquireCounts 1..7
@@ -344,10 +353,63 @@ class PackedBatch:
         if hb.origin is not None:
             self.origin = alloc((n,), np.uint32)
             self.origin[...] = hb.origin
+        self._pack_args(hb, alloc)
+        self.context = None
+        if hb.context is not None:
+            self.context = alloc((n,), np.uint32)
+            self.context[...] = hb.context
+
+    def _pack_args(self, hb: "HostBatch", alloc):
+        """The values in event order, slot order within an event; the element
+        CSR re-indexed by value (the SoA form's is indexed slot * n + event)."""
+        n = hb.n
+        self.n_arg_events = self.n_values = self.arg_slots = self.n_elems = 0
+        self.arg_event = self.arg_off = self.arg_tag = self.arg_bits = None
+        self.elem_off = self.elem_tag = self.elem_bits = None
+        slots = 0 if hb.arg_tag is None else hb.arg_tag.shape[0]
+        if not n or not slots:
+            return
+        na = np.full(n, slots, np.int64) if hb.n_args is None else hb.n_args.astype(np.int64)
+        if na.max() > slots:
+            raise ValueError("n_args above arg_slots")
+        listed = np.nonzero(na > 0)[0]
+        if not listed.size:
+            return
+        self.arg_slots = slots
+        full = listed.size == n and int(na.min()) == slots
+        cnt = na[listed]
+        has = np.arange(slots)[None, :] < cnt[:, None]             # [listed, slot]
+        ev_i = np.broadcast_to(listed[:, None], has.shape)[has]    # the event and slot of each value
+        sl_i = np.broadcast_to(np.arange(slots)[None, :], has.shape)[has]
+        self.n_arg_events, self.n_values = int(listed.size), int(ev_i.size)
+        self.arg_tag = alloc((ev_i.size,), np.uint8)
+        self.arg_tag[...] = hb.arg_tag[sl_i, ev_i]
+        self.arg_bits = alloc((ev_i.size,), np.uint64)
+        self.arg_bits[...] = hb.arg_bits[sl_i, ev_i]
+        if not full:
+            self.arg_event = alloc((listed.size,), np.uint32)
+            self.arg_event[...] = listed
+            self.arg_off = alloc((listed.size + 1,), np.uint32)
+            self.arg_off[0] = 0
+            self.arg_off[1:] = np.cumsum(cnt)
+        if hb.elem_off is not None:
+            k = sl_i * n + ev_i
+            lo = hb.elem_off[k].astype(np.int64)
+            ln = np.where(hb.arg_tag[sl_i, ev_i] == TAG_COLLECTION, hb.elem_off[k + 1].astype(np.int64) - lo, 0)
+            off = np.concatenate([[0], np.cumsum(ln)])
+            src = np.repeat(lo - off[:-1], ln) + np.arange(int(off[-1]))
+            self.n_elems = int(off[-1])
+            self.elem_off = alloc((off.size,), np.uint32)
+            self.elem_off[...] = off
+            self.elem_tag = alloc((self.n_elems,), np.uint8)
+            self.elem_tag[...] = hb.elem_tag[src]
+            self.elem_bits = alloc((self.n_elems,), np.uint64)
+            self.elem_bits[...] = hb.elem_bits[src]
 
     def nbytes(self) -> int:
         return sum(a.nbytes for a in (self.ev, self.ev4, self.ms_end, self.exit_ref, self.exit_cts, self.count_ext,
-                                      self.origin) if a is not None)
+                                      self.origin, self.arg_event, self.arg_off, self.arg_tag, self.arg_bits,
+                                      self.elem_off, self.elem_tag, self.elem_bits, self.context) if a is not None)
 
     def c_struct(self) -> sf_packed_batch:
         b = sf_packed_batch()
@@ -356,6 +418,11 @@ class PackedBatch:
         b.count_ext, b.origin = _ptr(self.count_ext), _ptr(self.origin)
         b.n_exit, b.n_count_ext = self.n_exit, self.n_count_ext
         b.ev4, b.ms_end, b.n_ms = _ptr(self.ev4), _ptr(self.ms_end), self.n_ms
+        b.n_arg_events, b.n_values, b.arg_slots, b.n_elems = self.n_arg_events, self.n_values, self.arg_slots, self.n_elems
+        b.arg_event, b.arg_off, b.arg_tag, b.arg_bits = (_ptr(self.arg_event), _ptr(self.arg_off), _ptr(self.arg_tag),
+                                                       _ptr(self.arg_bits))
+        b.elem_off, b.elem_tag, b.elem_bits = _ptr(self.elem_off), _ptr(self.elem_tag), _ptr(self.elem_bits)
+        b.context = _ptr(self.context)
         return b
 
 

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "sf_decide.h"
+#include "sf_pkargs.h"
 #include "sf_xflow.h"
 #include "sf_sysx.h"
 #include "sf_token.h"
@@ -66,6 +67,11 @@ struct StageBuf {
 // one slot's batch, its SoA expansion and the verdicts copied back
 struct PkStage {
     char* buf = nullptr; size_t bytes = 0;
+    // ParamFlow arguments, elements, contexts (and staged origins), sized by the
+    // batch: [0, a_in) the staged sparse inputs (free at `consumed`), [a_in,
+    // a_in + a_x) what the expansion writes and the decide phase reads (free at
+    // the slot's `end`).  The boundary moves only when the buffer is reallocated.
+    char* abuf = nullptr; size_t a_in = 0, a_x = 0;
     hipEvent_t h2d = nullptr, d2h = nullptr;
     hipEvent_t consumed = nullptr;     // the packed inputs expanded (the next H2D into them may start)
     bool d2h_pending = false, consumed_pending = false;
@@ -270,6 +276,7 @@ static void slot_destroy(Slot& sl) {
     free_work(sl.w);
     PkStage& p = sl.pk;
     if (p.buf) hipFree(p.buf);
+    if (p.abuf) hipFree(p.abuf);
     if (p.err_host) hipHostFree(p.err_host);
     if (p.sp_counts) hipHostFree(p.sp_counts);
     for (hipEvent_t x : {p.h2d, p.d2h, p.consumed, sl.sorted, sl.done, sl.end, sl.core}) if (x) hipEventDestroy(x);
@@ -1105,14 +1112,15 @@ static int check_event_batch(const sf_engine* e, const sf_event_batch* in) {
 // The origin-node pool on its first use (every entry with an origin has a node,
 // ClusterBuilderSlot.java:107-110; the caller has drained) and room in the
 // ParamFlow table for every key the batch can insert.
-static int reserve_for_batch(sf_engine* e, const sf_event_batch* in, bool with_ox) {
+static int reserve_for_batch(sf_engine* e, const sf_event_batch* in, bool with_ox, uint32_t n_arg_events) {
     if (with_ox && !e->st.xtab) {
         const int rc = ensure_aux(e);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(e->stream));
     }
     const uint64_t elems = in->arg_elem_off ? in->n_elems : 0;
-    return param_reserve(e, ((uint64_t)in->n + elems) * e->p_kmax);
+    // (an event without arguments reaches no parameter map)
+    return param_reserve(e, ((uint64_t)n_arg_events + elems) * e->p_kmax);
 }
 
 // the batch that last used the next batch's slot (two submits ago) must be done:
@@ -1203,6 +1211,10 @@ static int decide_view(sf_engine* e, Slot& sl, DevState& stl, const DevBatch& b,
 // pre: launched on the sort stream after the batch's error flag is cleared and
 // before its sort (sf_submit_packed's expansion of the packed words)
 using PreSort = std::function<hipError_t(hipStream_t, int32_t*)>;
+// what sf_submit_packed adds to the batch it hands to submit_core: the
+// expansion, whether a collection's abits is its CSR index already
+// (DevBatch::acsr), and the events that can reach a parameter map
+struct PackedHook { PreSort pre; bool acsr; uint32_t n_arg_events; };
 
 // A staged batch under SystemRules on an unsharded engine.  They couple every
 // IN entry to the global ENTRY_NODE: the batch is decided as a sequence of
@@ -1252,7 +1264,7 @@ static int submit_sys_rounds(sf_engine* e, Slot& sl, const DevBatch& b, const De
 }
 
 static int submit_core(sf_engine* e, const sf_event_batch* in, sf_verdicts* out, bool async,
-                       const uint8_t* forced = nullptr, const PreSort* pre = nullptr) {
+                       const uint8_t* forced = nullptr, const PackedHook* hook = nullptr) {
     if (!e || !in || !out || !out->status) return fail(SF_ERR_INVALID, "null argument");
     if (in->n == 0) return SF_OK;
     { const int rc = check_event_batch(e, in); if (rc) return rc; }
@@ -1270,7 +1282,8 @@ static int submit_core(sf_engine* e, const sf_event_batch* in, sf_verdicts* out,
     async = async && in->mem != SF_MEM_HOST && out->mem != SF_MEM_HOST && !e->sys.check && !forced;
     // (the first batch with origins builds the origin-node pool with nothing in flight)
     if (!async || (with_ox && !e->st.xtab)) { const int rc = drain(e); if (rc) return rc; }
-    { const int rc = reserve_for_batch(e, in, with_ox); if (rc) return rc; }
+    { const int rc = reserve_for_batch(e, in, with_ox, hook ? hook->n_arg_events : in->n); if (rc) return rc; }
+    const PreSort* pre = hook ? &hook->pre : nullptr;
     for (Slot& x : e->slot) {                      // the other Work sets on first asynchronous use
         if (!async || x.ready) continue;
         HIP_TRY(hipStreamSynchronize(s));
@@ -1283,6 +1296,7 @@ static int submit_core(sf_engine* e, const sf_event_batch* in, sf_verdicts* out,
     DevBatch b{};
     DevVerdicts dv{};
     { const int rc = stage_batch(e, in, out, ss, b, dv); if (rc) return rc; }
+    b.acsr = hook && hook->acsr;
     if (forced) {
         // the forced SystemRule verdicts of this (sub-)batch, planned node-wide
         { const int rc = sys_buffers_ensure(e); if (rc) return rc; }
@@ -1384,6 +1398,15 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
         return fail(SF_ERR_INVALID, "missing packed arrays");
     if (narrow && in->n_ms > SF_PK4_MAX_MS) return fail(SF_ERR_INVALID, "narrow packed batch spans more than 2^20 ms");
     if (in->n > e->cfg.max_batch) return fail(SF_ERR_CAPACITY, "batch larger than max_batch");
+    // ParamFlow arguments, collection elements, contexts (sf_pkargs.h): what the
+    // scalars tell is refused here, what the tables hold by the expansion
+    PkArgIn ai{in->n, in->n_arg_events, in->n_values, in->arg_slots, in->n_elems, in->arg_event, in->arg_off,
+               in->arg_tag, in->arg_bits, in->elem_off};
+    if (!pk_args_header_ok(ai)) return fail(SF_ERR_INVALID, "bad packed argument tables");
+    if (!ai.n_values) ai.elem_off = nullptr;                   // (no value: no collection)
+    if (!ai.elem_off) ai.n_elems = 0;
+    if (ai.n_elems && (!in->elem_tag || !in->elem_bits))
+        return fail(SF_ERR_INVALID, "collection arguments without element arrays");
     std::lock_guard<std::mutex> lk(e->mu);
     const uint32_t n = in->n;
     const bool host_in = in->mem == SF_MEM_HOST, host_out = sp || out->mem == SF_MEM_HOST;
@@ -1431,11 +1454,52 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
         pk.bytes = off;
     }
     char* B = pk.buf;
+    // The arguments, elements and contexts are sized by the batch, not by
+    // max_batch, so they have a buffer of their own (pk.buf's offsets are fixed
+    // and batches in flight point into it).  Two lifetimes: the staged sparse
+    // inputs are free once expanded (`consumed`), the dense arrays, the copied
+    // elements and contexts are read by the decide phase and live until the
+    // slot's `end`, like the expanded SoA arrays -- which is why the expansion
+    // copies elements and contexts instead of handing on the staged ones.
+    // The staged origins follow the same rule: the xflow walk reads them in
+    // submission order during the decide phase, and the next H2D copy into
+    // this slot waits only for `consumed`.
+    const bool args = ai.n_arg_events != 0, ctx = in->context != nullptr, og_copy = host_in && in->origin;
+    const uint32_t nae = ai.n_arg_events, nv = ai.n_values, ne = ai.n_elems, slots = args ? ai.arg_slots : 0;
+    size_t aoff = 0;
+    auto atake = [&](bool on, size_t bytes) { const size_t o = aoff; if (on) aoff += align_up(bytes); return o; };
+    const bool st = host_in;                                   // staged inputs (device batches are read in place)
+    const size_t i_ae = atake(st && args && ai.arg_event, (size_t)nae * 4), i_ao = atake(st && args && ai.arg_off, ((size_t)nae + 1) * 4);
+    const size_t i_at = atake(st && nv, nv), i_ab = atake(st && nv, (size_t)nv * 8);
+    const size_t i_eo = atake(st && ai.elem_off, ((size_t)nv + 1) * 4), i_et = atake(st && ne, ne), i_eb = atake(st && ne, (size_t)ne * 8);
+    const size_t i_cx = atake(st && ctx, (size_t)n * 4);
+    const size_t need_in = aoff;
+    aoff = 0;
+    const size_t x_na = atake(args, n), x_at = atake(args, (size_t)n * slots), x_ab = atake(args, (size_t)n * slots * 8);
+    const size_t x_eo = atake(ai.elem_off, ((size_t)nv + 1) * 4), x_et = atake(ne, ne), x_eb = atake(ne, (size_t)ne * 8);
+    const size_t x_cx = atake(ctx, (size_t)n * 4), x_og = atake(og_copy, (size_t)n * 4);
+    const size_t need_x = aoff;
+    if (need_in > pk.a_in || need_x > pk.a_x) {
+        if (sl.used) HIP_TRY(hipEventSynchronize(sl.end));
+        if (pk.consumed_pending) { HIP_TRY(hipEventSynchronize(pk.consumed)); pk.consumed_pending = false; }
+        if (pk.d2h_pending) { HIP_TRY(hipEventSynchronize(pk.d2h)); pk.d2h_pending = false; }
+        if (pk.abuf) hipFree(pk.abuf);
+        pk.abuf = nullptr;
+        const size_t c_in = std::max(need_in, pk.a_in), c_x = std::max(need_x, pk.a_x);
+        pk.a_in = pk.a_x = 0;
+        HIP_TRY(hipMalloc((void**)&pk.abuf, c_in + c_x));
+        pk.a_in = c_in; pk.a_x = c_x;
+    }
+    char* AI = pk.abuf;                                        // staged inputs
+    // the expanded region (no buffer: the batch needs none, and no offset is taken)
+    auto ax = [&](bool on, size_t o) -> char* { return on && pk.abuf ? pk.abuf + pk.a_in + o : nullptr; };
     hipStream_t ss = e->serial ? e->stream : e->sstream;
     const uint64_t* ev = in->ev; const int64_t* xr = in->exit_ref; const int64_t* xc = in->exit_cts;
     const uint32_t* ev4 = narrow ? in->ev4 : nullptr; const uint32_t* mse = narrow ? in->ms_end : nullptr;
     const uint32_t n_ms = narrow ? in->n_ms : 0;
     const int32_t* ce = in->count_ext; const uint32_t* og = in->origin;
+    PkCopy cp{};                                               // sources: the caller's device arrays, or the staged ones
+    cp.etag = ne ? in->elem_tag : nullptr; cp.ebits = ne ? in->elem_bits : nullptr; cp.ctx = in->context;
     if (host_in) {
         hipStream_t h = e->serial ? e->stream : e->h2d;
         if (pk.consumed_pending) HIP_TRY(hipStreamWaitEvent(h, pk.consumed, 0));
@@ -1464,6 +1528,25 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
             HIP_TRY(hipMemcpyAsync(B + o_og, in->origin, (size_t)n * 4, hipMemcpyHostToDevice, h));
             og = (const uint32_t*)(B + o_og);
         }
+        hipError_t ue = hipSuccess;
+        auto up = [&](size_t o, const void* src, size_t bytes) -> const void* {
+            if (!src || !bytes) return nullptr;
+            const hipError_t he = hipMemcpyAsync(AI + o, src, bytes, hipMemcpyHostToDevice, h);
+            if (he != hipSuccess) ue = he;
+            return AI + o;
+        };
+        if (args) {
+            ai.arg_event = (const uint32_t*)up(i_ae, in->arg_event, (size_t)nae * 4);
+            ai.arg_off = (const uint32_t*)up(i_ao, in->arg_off, ((size_t)nae + 1) * 4);
+            ai.arg_tag = (const uint8_t*)up(i_at, in->arg_tag, nv);
+            ai.arg_bits = (const uint64_t*)up(i_ab, in->arg_bits, (size_t)nv * 8);
+            ai.elem_off = (const uint32_t*)up(i_eo, ai.elem_off, ((size_t)nv + 1) * 4);
+        }
+        cp.etag = (const uint8_t*)up(i_et, ne ? in->elem_tag : nullptr, ne);
+        cp.ebits = (const uint64_t*)up(i_eb, ne ? in->elem_bits : nullptr, (size_t)ne * 8);
+        cp.ctx = (const uint32_t*)up(i_cx, in->context, (size_t)n * 4);
+        if (ue != hipSuccess) return fail(SF_ERR_DEVICE, std::string("packed H2D: ") + hipGetErrorString(ue));
+        if (og_copy) cp.origin = og;
         HIP_TRY(hipEventRecord(pk.h2d, h));
         HIP_TRY(hipStreamWaitEvent(ss, pk.h2d, 0));
     }
@@ -1471,12 +1554,21 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
     const int64_t base = in->ts_base;
     const uint32_t n_exit = in->n_exit, n_cext = in->n_count_ext;
     const hipEvent_t consumed = pk.consumed;
+    if (!args) { ai.n_arg_events = ai.n_values = 0; ai.arg_event = ai.arg_off = nullptr; ai.elem_off = nullptr; }
+    const PkArgOut ao{(uint8_t*)ax(args, x_na), (uint8_t*)ax(args, x_at), (uint64_t*)ax(args, x_ab),
+                      (uint32_t*)ax(ai.elem_off != nullptr, x_eo)};
+    cp.etag_out = (uint8_t*)ax(ne != 0, x_et); cp.ebits_out = (uint64_t*)ax(ne != 0, x_eb);
+    cp.ctx_out = (uint32_t*)ax(ctx, x_cx); cp.origin_out = (uint32_t*)ax(og_copy, x_og);
     const PreSort expand = [=](hipStream_t st_, int32_t* err) {
         const hipError_t le = launch_pk_expand(ev, ev4, mse, n_ms, xr, xc, ce, base, n, n_exit, n_cext, (uint2*)(B + o_tc),
                                                (uint32_t*)(B + o_res), (int64_t*)(B + o_ts), (int32_t*)(B + o_cnt),
                                                (uint8_t*)(B + o_fl), (int64_t*)(B + o_er),
                                                exits ? (int64_t*)(B + o_ct) : nullptr, err, st_);
         if (le != hipSuccess) return le;
+        if (args || cp.etag || cp.ctx || cp.origin) {
+            const hipError_t ae = launch_pk_args(ai, ao, cp, err, st_);
+            if (ae != hipSuccess) return ae;
+        }
         return hipEventRecord(consumed, st_);
     };
     if (pk.d2h_pending) { HIP_TRY(hipStreamWaitEvent(ss, pk.d2h, 0)); pk.d2h_pending = false; }
@@ -1486,7 +1578,15 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
     eb.count = (const int32_t*)(B + o_cnt); eb.flags = (const uint8_t*)(B + o_fl);
     eb.entry_ref = exits ? (const int64_t*)(B + o_er) : nullptr;
     eb.create_ts = exits ? (const int64_t*)(B + o_ct) : nullptr;
-    eb.origin = og;
+    eb.origin = cp.origin ? cp.origin_out : og;
+    if (args) {
+        eb.arg_slots = slots; eb.n_args = ao.nargs; eb.arg_tag = ao.atag; eb.arg_bits = ao.abits;
+        if (ai.elem_off) {
+            eb.arg_elem_off = ao.eoff; eb.n_elems = ne;
+            eb.elem_tag = cp.etag_out; eb.elem_bits = cp.ebits_out;
+        }
+    }
+    if (ctx) eb.context = cp.ctx_out;
     sf_verdicts dv{};
     dv.mem = SF_MEM_DEVICE;
     dv.status = host_out ? (uint8_t*)(B + o_st) : out->status;
@@ -1495,7 +1595,8 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
     // (the expansion rewrites the arrays the ENTRY_NODE update of this slot's
     // previous batch reads)
     if (sl.used) HIP_TRY(hipStreamWaitEvent(ss, sl.end, 0));
-    const int rc = submit_core(e, &eb, &dv, core_async, nullptr, &expand);
+    const PackedHook hook{expand, ai.elem_off != nullptr, nae};
+    const int rc = submit_core(e, &eb, &dv, core_async, nullptr, &hook);
     if (rc) return rc;
     pk.consumed_pending = true;
     if (host_out) {
@@ -1700,7 +1801,7 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
     { const int rc = sys_buffers_ensure(e); if (rc) return rc; }
     { const int rc = sx_recv_reserve(e, (size_t)N * SX_WORDS); if (rc) return rc; }
     const bool with_ox = in->origin || e->st.xmap;
-    { const int rc = reserve_for_batch(e, in, with_ox); if (rc) return rc; }
+    { const int rc = reserve_for_batch(e, in, with_ox, in->n); if (rc) return rc; }
     Slot& sl = e->slot[e->cur];
     { const int rc = take_slot(e, sl); if (rc) return rc; }
     Work& w = sl.w;

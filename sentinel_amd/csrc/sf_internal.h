@@ -293,6 +293,9 @@ struct DevBatch {
     uint32_t arg_slots; const uint8_t* nargs; const uint8_t* atag; const uint64_t* abits;
     uint32_t arg_stride;           // slot stride of atag / abits (the whole batch's n)
     const uint32_t* aoff; const uint8_t* etag; const uint64_t* ebits;   // collection elements (batch-wide CSR)
+    // 0: the CSR is slot-major like atag (a collection at slot a of event i is entry a*stride + i);
+    // 1: abits of a collection argument already holds its CSR index (a packed batch's value index)
+    uint32_t acsr;
     const uint32_t* origin; const uint32_t* ctx;   // context of each event (or null)
     int64_t base;                  // index of the view's first event in the batch (0: whole batch)
     const uint8_t* sys;            // planner verdicts of IN entries (SYS_NONE: none), or null
@@ -369,6 +372,15 @@ hipError_t launch_pk_expand(const uint64_t* ev, const uint32_t* ev4, const uint3
                             int64_t base, uint32_t n, uint32_t n_exit, uint32_t n_cext, uint2* tile_cnt,
                             uint32_t* res, int64_t* ts, int32_t* cnt, uint8_t* flags, int64_t* eref, int64_t* cts,
                             int32_t* err, hipStream_t s);
+// sf_packed_batch's arguments, elements and contexts -> the dense arrays of the
+// decide phase (sf_pkargs.h); also the staged origins into the expanded region.
+// Every destination lives until the batch is decided; a malformed table raises err.
+struct PkArgIn; struct PkArgOut;
+struct PkCopy {                                  // [n_elems] elements, [n] contexts / origins; null source: none
+    const uint8_t* etag; const uint64_t* ebits; uint8_t* etag_out; uint64_t* ebits_out;
+    const uint32_t* ctx; uint32_t* ctx_out; const uint32_t* origin; uint32_t* origin_out;
+};
+hipError_t launch_pk_args(const PkArgIn& in, const PkArgOut& out, const PkCopy& cp, int32_t* err, hipStream_t s);
 // sf_sparse_verdicts: the nonzero waits / rule indices of n verdicts as (index << 32 | value) lists
 hipError_t launch_sparse_verdicts(const int32_t* wait, const uint16_t* rule, uint32_t n, unsigned long long* wl,
                                   unsigned long long* rl, uint32_t* counts, hipStream_t s);

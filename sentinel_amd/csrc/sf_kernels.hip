@@ -24,6 +24,7 @@
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
+#include "sf_pkargs.h"
 #include "sf_rsort.h"
 #include "sf_stream.h"
 #include "sf_system.h"
@@ -2713,6 +2714,57 @@ hipError_t launch_sparse_verdicts(const int32_t* wait, const uint16_t* rule, uin
     hipMemsetAsync(counts, 0, 8, s);
     if (n) hipLaunchKernelGGL(k_sparse_verdicts, dim3((n + SV_TILE - 1) / SV_TILE), dim3(SV_T), 0, s, wait, rule, n,
                               wl, rl, counts);
+    return hipGetLastError();
+}
+
+// The arguments, elements and contexts of a packed batch (sf_pkargs.h), after
+// nargs / atag are zero-filled on the same stream, in two grid-stride passes.
+// k_pk_args_check validates every listed entry and every entry of the element
+// CSR (copying the CSR, clamped to n_elems) and raises the batch's error flag
+// on any defect.  k_pk_args then expands the listed events into the dense
+// slot-major arrays -- only when the flag is clear, so the verdict is global:
+// a refused table leaves every event without arguments, and in an accepted
+// one exactly one thread writes an event (arg_event is strictly increasing
+// as a whole).  The same pass copies elements, contexts and origins into the
+// expanded region, which outlives the staged inputs.
+constexpr uint32_t PKA_T = 256, PKA_MAX_BLOCKS = 2048;
+__global__ void __launch_bounds__(PKA_T) k_pk_args_check(PkArgIn in, PkArgOut out, uint32_t span, int32_t* err) {
+    bool bad = false;
+    for (uint32_t t = blockIdx.x * PKA_T + threadIdx.x; t < span; t += gridDim.x * PKA_T) {
+        if (t < in.n_arg_events) bad |= !pk_args_event_ok(in, t);
+        if (in.elem_off && t <= in.n_values) bad |= !pk_args_elem_off(in, out, t);
+    }
+    if (bad) *err = SF_ERR_INVALID;
+}
+__global__ void __launch_bounds__(PKA_T) k_pk_args(PkArgIn in, PkArgOut out, PkCopy cp, uint32_t span, const int32_t* err) {
+    // (the flag of the whole batch, k_pk_scan's included: an errored batch carries no arguments)
+    const bool expand = *err == 0;
+    for (uint32_t t = blockIdx.x * PKA_T + threadIdx.x; t < span; t += gridDim.x * PKA_T) {
+        if (expand && t < in.n_arg_events) pk_args_event_put(in, out, t);
+        if (cp.etag && t < in.n_elems) { cp.etag_out[t] = cp.etag[t]; cp.ebits_out[t] = cp.ebits[t]; }
+        if (t < in.n) {
+            if (cp.ctx) cp.ctx_out[t] = cp.ctx[t];
+            if (cp.origin) cp.origin_out[t] = cp.origin[t];
+        }
+    }
+}
+hipError_t launch_pk_args(const PkArgIn& in, const PkArgOut& out, const PkCopy& cp, int32_t* err, hipStream_t s) {
+    auto blocks = [](uint32_t span) { const uint32_t nb = (span + PKA_T - 1) / PKA_T; return nb < PKA_MAX_BLOCKS ? nb : PKA_MAX_BLOCKS; };
+    uint32_t span = 0;
+    if (in.n_arg_events) {
+        // (the final sort pass gathers every slot of every event: the bytes no listed event writes are zero)
+        hipError_t me = hipMemsetAsync(out.nargs, 0, in.n, s);
+        if (me == hipSuccess) me = hipMemsetAsync(out.atag, 0, (size_t)in.n * in.arg_slots, s);
+        if (me != hipSuccess) return me;
+        span = in.n_arg_events;
+        if (in.elem_off && in.n_values + 1 > span) span = in.n_values + 1;
+        hipLaunchKernelGGL(k_pk_args_check, dim3(blocks(span)), dim3(PKA_T), 0, s, in, out, span, err);
+        span = in.n_arg_events;
+    }
+    if (cp.etag && in.n_elems > span) span = in.n_elems;
+    if ((cp.ctx || cp.origin) && in.n > span) span = in.n;
+    if (!span) return hipGetLastError();
+    hipLaunchKernelGGL(k_pk_args, dim3(blocks(span)), dim3(PKA_T), 0, s, in, out, cp, span, (const int32_t*)err);
     return hipGetLastError();
 }
 

@@ -246,8 +246,10 @@ struct RsSinkFinal {
                 const uint8_t tg = b.atag[(size_t)a * b.arg_stride + i];
                 s_atag[(size_t)a * b.n + j] = tg;
                 // a collection argument carries its index into the batch's element CSR
-                s_abits[(size_t)a * b.n + j] = tg == SF_TAG_COLLECTION ? (uint64_t)a * b.arg_stride + (uint64_t)b.base + i
-                                                                      : b.abits[(size_t)a * b.arg_stride + i];
+                // (a packed batch's abits holds it already: DevBatch::acsr)
+                s_abits[(size_t)a * b.n + j] = (tg == SF_TAG_COLLECTION && !b.acsr)
+                                                   ? (uint64_t)a * b.arg_stride + (uint64_t)b.base + i
+                                                   : b.abits[(size_t)a * b.arg_stride + i];
             }
         }
     }
