@@ -24,6 +24,8 @@
 #include "sf_concur.h"
 #include "sf_wire.h"
 #include "sf_degrade.h"
+#include "sf_mem.h"
+#include "sf_worksets.h"
 #include <rccl/rccl.h>
 #include <functional>
 #include <unordered_map>
@@ -44,21 +46,36 @@ static int fail(int code, const std::string& msg) {
                         std::string(#expr ": ") + hipGetErrorString(_e));               \
     } while (0)
 
+// The backend of sf_mem.h: the only place where device and pinned host memory
+// is allocated or freed.  Every pointer belongs to a DevPool: the engine's, a
+// slot's two, a work set's, or a call's scratch pool (freed when the call returns).
+static int hip_alloc_failed(const char* what, hipError_t e) {
+    return fail(SF_ERR_NOMEM, std::string(what) + ": " + hipGetErrorString(e));
+}
+static int hip_dev_alloc(void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    return e == hipSuccess ? SF_OK : hip_alloc_failed("hipMalloc", e);
+}
+static int hip_host_alloc(void** p, size_t bytes) {
+    const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
+    return e == hipSuccess ? SF_OK : hip_alloc_failed("hipHostMalloc", e);
+}
+static const MemOps HIP_MEM{hip_dev_alloc, [](void* p) { hipFree(p); }, hip_host_alloc, [](void* p) { hipHostFree(p); }};
+
 // cluster concurrency tokens (sf_concur.hip): the device state with the host's
 // view of it as of the last call
 struct CcHost {
     CcState cs{};
-    CcWork w{};
+    CcWorkSet ws{HIP_MEM};
     CcCounters ctr{};                 // device counters after the last call (ctr.top: free slots)
     uint64_t grows = 0;
     std::vector<sf_concurrent_config> cfg;    // sf_load_concurrent_config
-    void* stage = nullptr; size_t stage_bytes = 0;
-    uint8_t* online = nullptr; size_t online_bytes = 0;
+    GrowBuf stage, online;
 };
 
 // a device copy of host event arrays, remembered by their addresses (stage_in_events)
 struct StageBuf {
-    void* p = nullptr; size_t bytes = 0; const void* key[5] = {}; uint32_t n = 0;
+    GrowBuf buf; const void* key[5] = {}; uint32_t n = 0;
     int64_t fp[3] = {};                                     // ts[0], ts[n-1], flags[0] of the staged arrays
     const uint8_t* st_src = nullptr; uint32_t st_n = 0;    // verdicts [0, st_n) of st_src already staged
 };
@@ -66,12 +83,12 @@ struct StageBuf {
 // compact batches (sf_submit_packed): the device copy of the packed input of
 // one slot's batch, its SoA expansion and the verdicts copied back
 struct PkStage {
-    char* buf = nullptr; size_t bytes = 0;
+    GrowBuf buf;
     // ParamFlow arguments, elements, contexts (and staged origins), sized by the
     // batch: [0, a_in) the staged sparse inputs (free at `consumed`), [a_in,
     // a_in + a_x) what the expansion writes and the decide phase reads (free at
     // the slot's `end`).  The boundary moves only when the buffer is reallocated.
-    char* abuf = nullptr; size_t a_in = 0, a_x = 0;
+    GrowBuf abuf; size_t a_in = 0, a_x = 0;
     hipEvent_t h2d = nullptr, d2h = nullptr;
     hipEvent_t consumed = nullptr;     // the packed inputs expanded (the next H2D into them may start)
     bool d2h_pending = false, consumed_pending = false;
@@ -93,6 +110,7 @@ struct PkStage {
 constexpr int SF_SLOTS = 2;
 struct Slot {
     Work w{};                       // the sorted-order buffers (allocated on first use: ready)
+    DevPool wpool{HIP_MEM};         // owns them
     bool ready = false;
     bool used = false;              // a batch has been enqueued into the slot (its events are recorded)
     bool timed = false;             // that batch ran with timing on and is not yet in stats
@@ -102,10 +120,15 @@ struct Slot {
     hipEvent_t core = nullptr;      // its verdicts are written (the packed D2H copy waits for it)
     hipEvent_t evs[SF_NUM_EVENTS]{};   // fork / join and timing events of its batch
     PkStage pk;
+    DevPool pkpool{HIP_MEM};        // owns the packed stage's buffers
 };
 
 struct sf_engine {
     sf_config cfg{};
+    // owns everything below that has no pool of its own: the state tables, the
+    // rule tables, the staging buffers, the origin / context node pool
+    DevPool pool{HIP_MEM};
+    DevPool user_dev{HIP_MEM}, user_host{HIP_MEM};   // sf_device_alloc / sf_host_alloc
     hipStream_t stream = nullptr, stream2 = nullptr, stream3 = nullptr, stream4 = nullptr;   // 4: the wave walk
     hipStream_t sstream = nullptr;  // sort phase of the next batch (overlaps the decide phase on `stream`)
     // ENTRY_NODE's update of an asynchronous batch (after its verdicts, beside
@@ -135,27 +158,23 @@ struct sf_engine {
     // batches enqueued since; the most keys one event can insert
     uint64_t p_used = 0, p_pending = 0, p_kmax = 0, p_grows = 0;
     // staging for host-memory batches
-    void* stage_in = nullptr; size_t stage_in_bytes = 0;
-    void* stage_out = nullptr; size_t stage_out_bytes = 0;
+    GrowBuf stage_in, stage_out;
     StageBuf plan_sb, en_sb;                       // sf_system_plan / sf_entry_node_add inputs
     bool timing = false;
     sf_stats stats{};
-    std::vector<void*> user_allocs;
-    std::vector<void*> host_allocs;      // sf_host_alloc (pinned host memory)
     std::mutex mu;
     // cluster token server (sf_token.hip)
     TokState ts{};
-    TokWork tw{};
-    uint32_t tw_cap = 0;
+    TokWorkSet tw{HIP_MEM};
     std::vector<sf_namespace> host_ns;
     std::vector<sf_cluster_flow_rule> host_cflow;
     std::vector<sf_cluster_param_rule> host_cparam;
     std::vector<sf_hot_item> host_citems;
     std::vector<int64_t> cflow_ids;           // flow rule index -> flowId
-    void* tok_stage = nullptr; size_t tok_stage_bytes = 0;
+    GrowBuf tok_stage;
     CcHost cc;
     int64_t* d_sum = nullptr;
-    void* wire_arena = nullptr; size_t wire_bytes = 0;   // sf_serve_frames scratch (grow-only)
+    GrowBuf wire_arena;                                  // sf_serve_frames scratch
     // ENTRY_NODE and the metric snapshot (sf_entry.hip)
     EntryNode* en = nullptr;
     EntryAcc* en_acc = nullptr;
@@ -164,32 +183,36 @@ struct sf_engine {
     EntryNode report{};
     EntryNode* en_report = nullptr;    // device staging of `report` for the metric kernels
     uint32_t* snap_counts = nullptr; uint32_t* snap_offsets = nullptr; uint32_t* snap_total = nullptr;
-    sf_metric_row* snap_rows = nullptr; uint32_t snap_cap = 0;
     void* snap_scan = nullptr; size_t snap_scan_bytes = 0;
+    bool snap_ready = false;           // the four above are allocated
+    GrowBuf snap_rows;
     // metrics.log (sf_metric.hip)
     char* nm_bytes = nullptr; uint64_t* nm_off = nullptr; int32_t* nm_types = nullptr; uint32_t n_names = 0;
-    unsigned long long* ml_mask = nullptr; uint32_t* ml_counts = nullptr; uint32_t* ml_offsets = nullptr;
-    uint32_t* ml_total = nullptr;
-    sf_metric_row* ml_rows = nullptr; uint8_t* ml_keys = nullptr; uint32_t* ml_order = nullptr; uint32_t ml_row_cap = 0;
-    uint64_t* ml_len = nullptr; uint64_t* ml_off = nullptr; uint64_t* ml_bytes = nullptr;
-    char* ml_out = nullptr; uint64_t ml_out_cap = 0;
-    void* ml_tmp = nullptr; size_t ml_tmp_bytes = 0;
+    struct MetricLog {                 // ml_reserve: the per-node buffers (ready) and the per-row ones (row_cap)
+        unsigned long long* mask = nullptr; uint32_t* counts = nullptr; uint32_t* offsets = nullptr;
+        uint32_t* total = nullptr; uint64_t* bytes = nullptr;
+        bool ready = false;
+        sf_metric_row* rows = nullptr; uint8_t* keys = nullptr; uint32_t* order = nullptr;
+        uint64_t* len = nullptr; uint64_t* off = nullptr; uint32_t row_cap = 0;
+        GrowBuf out, tmp;
+    } ml;
+    DevPool ml_pool{HIP_MEM};
     hipEvent_t ml_ev[3]{};
     // node-wide aggregate over the ranks of a node (RCCL over xGMI)
     ncclComm_t comm = nullptr;
     // sharded SystemRules, the per-window exchange (sf_sysx.h, sf_submit_node)
     int64_t* sx_msg = nullptr;            // this rank's message [SX_WORDS] (+ the setup words)
-    int64_t* sx_recv = nullptr; size_t sx_recv_words = 0;
+    GrowBuf sx_recv;
     int64_t* sx_seq = nullptr;            // [max_batch] device copy of host sequence numbers
     uint8_t* sx_ibuf = nullptr;           // [max_batch] inert flags of the round
     std::vector<int64_t> sx_hsend, sx_hrecv;   // host side of a callback all-gather
     int64_t* agg = nullptr;               // [ws (S+60) | gws (S+60) | vals ((S+60)*6+1) | minrt (S+60)]
     // DegradeSlot circuit breakers (sf_degrade.hip)
     DegradeDev dg{};
-    DegradeWork dgw{};
+    DegradeWorkSet dgw{HIP_MEM};
     std::vector<uint32_t> dg_pos;         // breaker index (load order) -> CSR position
     std::vector<sf_degrade_rule> dg_rules;   // the valid rules of the loaded breakers (load order)
-    void* dg_stage = nullptr; size_t dg_stage_bytes = 0;
+    GrowBuf dg_stage;
     // xflow walk (sf_xflow.h): group keys and the origin / context node pool
     uint32_t* xmap_buf = nullptr;
     uint8_t* xw_buf = nullptr;
@@ -202,25 +225,6 @@ struct sf_engine {
     hipStream_t h2d = nullptr, d2h = nullptr;
     int32_t* rh_err = nullptr;            // rehash_table's overflow flag
 };
-
-static void free_tok_work(TokWork& w) {
-    void* ptrs[] = {w.nskey_in, w.nskey_out, w.idx_in, w.idx_out, w.key_in, w.key_out, w.rule_of, w.pending,
-                    w.head, w.head_scan, w.seg_start, w.n_seg, w.sort8_tmp, w.sort64_tmp, w.scan_tmp};
-    for (void* p : ptrs) if (p) hipFree(p);
-    w = TokWork{};
-}
-
-static void free_cc_work(CcWork& w) {
-    void* ptrs[] = {w.key_in, w.key_out, w.idx_in, w.idx_out, w.delta, w.rslot, w.seg_lo, w.seg_hi, w.sort_tmp};
-    for (void* p : ptrs) if (p) hipFree(p);
-    w = CcWork{};
-}
-static void free_cc(CcHost& c) {
-    free_cc_work(c.w);
-    void* ptrs[] = {c.cs.slots, c.cs.stack, c.cs.claim, c.cs.now, (void*)c.cs.cfg, c.cs.ctr, c.stage, c.online};
-    for (void* p : ptrs) if (p) hipFree(p);
-    c.cs = CcState{};
-}
 
 extern "C" {
 
@@ -236,34 +240,6 @@ void sf_config_default(sf_config* c) {
     c->max_occupy_ratio = 1.0; c->max_flow_ids = 1024; c->aux_capacity = 65536;
 }
 
-static int dalloc(void** p, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) return fail(SF_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    return SF_OK;
-}
-#define DALLOC(ptr, bytes)                                               \
-    do {                                                                 \
-        int _rc = dalloc((void**)&(ptr), (bytes));                       \
-        if (_rc) { sf_destroy(e); return _rc; }                          \
-    } while (0)
-
-static void free_work(Work& w) {
-    void* ptrs[] = {w.pv_in, w.pv_out, w.err, w.keys_in, w.keys_out, w.perm, w.head, w.head_scan,
-                    w.seg_start, w.seg_res, w.n_seg, w.s_meta, w.s_eref,
-                    w.s_cts, w.s_nargs, w.s_atag, w.s_abits, w.v_status, w.v_wait,
-                    w.v_rule, w.sort_tmp, w.scan_tmp,
-                    w.segflag, w.seg_mode, w.light_list, w.lcounts, w.heavy_list, w.counters, w.pcg, w.segs_lb,
-                    w.pscan_tmp, w.fill_tiles, w.fill_ntiles, w.acc_hw,
-                    w.acc_sec, w.acc_hw_base, w.acc_sec_base, w.seg_hw0, w.seg_sec0,
-                    w.seg_nhw, w.seg_nsec, w.hticks, w.passbits, w.stream_list, w.xw_list, w.sticks,
-                    w.exit_of, w.lxfar, w.thr_rec, w.vs_cursor, w.tile_rc, w.seg_rb, w.seg_re,
-                    w.s_origin, w.s_oslot, w.ox_cnt, w.ox_bflags, w.ox_hmap, w.ox_hslot, w.ox_thr, w.ox_acc,
-                    w.ox_bseg, w.ox_pairs, w.ox_plist};
-    for (void* p : ptrs) if (p) hipFree(p);
-    w = Work{};
-}
-
 // the events of a slot (the packed stage's are created with its copy streams, submit_packed)
 static int slot_create(Slot& sl) {
     for (auto& x : sl.evs) HIP_TRY(hipEventCreate(&x));
@@ -272,79 +248,49 @@ static int slot_create(Slot& sl) {
     return SF_OK;
 }
 
-static void slot_destroy(Slot& sl) {
-    free_work(sl.w);
-    PkStage& p = sl.pk;
-    if (p.buf) hipFree(p.buf);
-    if (p.abuf) hipFree(p.abuf);
-    if (p.err_host) hipHostFree(p.err_host);
-    if (p.sp_counts) hipHostFree(p.sp_counts);
-    for (hipEvent_t x : {p.h2d, p.d2h, p.consumed, sl.sorted, sl.done, sl.end, sl.core}) if (x) hipEventDestroy(x);
-    for (hipEvent_t x : sl.evs) if (x) hipEventDestroy(x);
-}
-
+// Teardown: the streams drain, the pools free their memory, then the
+// communicator, the events and the streams go.  (A pool missing here would
+// still be freed by its destructor, after the streams.)
 void sf_destroy(sf_engine* e) {
     if (!e) return;
-    if (e->sstream) hipStreamSynchronize(e->sstream);
-    if (e->stream) hipStreamSynchronize(e->stream);
-    void* ptrs[] = {e->st.second, e->st.borrow, e->st.minute, e->st.threads, (void*)e->st.rule_off,
-                    (void*)e->st.rules, e->st.rstate, (void*)e->st.prule_off, e->st.prules, (void*)e->st.items,
-                    e->st.pm_init, e->st.ptab, e->st.err, e->stage_in, e->stage_out, e->plan_sb.p, e->en_sb.p, e->st.pins,
-                    e->st.xw_stats, (void*)e->st.rdesc, e->st.prio_seen, e->en_report, e->agg,
-                    (void*)e->ts.rules, e->ts.fstate, (void*)e->ts.idtab, (void*)e->ts.ns, e->ts.lim, e->ts.cptab,
-                    (void*)e->ts.items, e->ts.rmulti, e->tok_stage, e->wire_arena, e->d_sum, e->en, e->en_acc,
-                    e->snap_counts, e->snap_offsets, e->snap_total, e->snap_rows, e->snap_scan, e->st.last_fetch,
-                    e->st.last_ts, e->nm_bytes, e->nm_off, e->nm_types, e->ml_mask, e->ml_counts, e->ml_offsets,
-                    e->ml_total, e->ml_rows, e->ml_keys, e->ml_order, e->ml_len, e->ml_off, e->ml_bytes, e->ml_out,
-                    e->ml_tmp, e->sys_plan, e->sys_pa, e->sys_pb, e->sys_mask, e->sys_ibuf, e->sx_msg, e->sx_recv,
-                    e->sx_seq, e->sx_ibuf, e->xmap_buf, e->xw_buf, e->st.xtab, e->ax_dir, e->st.ax_count,
-                    (void*)e->dg.rr_of, (void*)e->dg.off, (void*)e->dg.rules, e->dg.state, e->dgw.keys_in,
-                    e->dgw.keys_out, e->dgw.idx_in, e->dgw.idx_out, e->dgw.beg, e->dgw.end, e->dgw.sort_tmp,
-                    e->dgw.err, e->rh_err, e->dg_stage, e->dgw.heavy, e->dgw.n_heavy, e->dgw.sev, e->dgw.inv};
-    for (void* p : ptrs) if (p) hipFree(p);
-    for (void* p : e->user_allocs) hipFree(p);
-    for (void* p : e->host_allocs) hipHostFree(p);
-    for (const AuxChunk& c : e->ax_host) hipFree(c.sec);          // (one allocation per chunk)
-    if (e->h2d) { hipStreamSynchronize(e->h2d); hipStreamDestroy(e->h2d); }
-    if (e->d2h) { hipStreamSynchronize(e->d2h); hipStreamDestroy(e->d2h); }
-    for (Slot& sl : e->slot) slot_destroy(sl);
+    for (hipStream_t x : {e->sstream, e->stream, e->h2d, e->d2h}) if (x) hipStreamSynchronize(x);
+    for (Slot& sl : e->slot) { sl.wpool.clear(); sl.pkpool.clear(); }
+    for (DevPool* p : {&e->pool, &e->user_dev, &e->user_host, &e->tw.pool, &e->cc.ws.pool, &e->dgw.pool, &e->ml_pool})
+        p->clear();
     if (e->comm) ncclCommDestroy(e->comm);
-    free_tok_work(e->tw);
-    free_cc(e->cc);
+    for (Slot& sl : e->slot) {
+        const PkStage& p = sl.pk;
+        for (hipEvent_t x : {p.h2d, p.d2h, p.consumed, sl.sorted, sl.done, sl.end, sl.core}) if (x) hipEventDestroy(x);
+        for (hipEvent_t x : sl.evs) if (x) hipEventDestroy(x);
+    }
     for (auto& x : e->ml_ev) if (x) hipEventDestroy(x);
-    for (hipStream_t x : {e->stream, e->stream2, e->stream3, e->stream4, e->sstream}) if (x) hipStreamDestroy(x);
-    if (e->enstream && e->en_own) hipStreamDestroy(e->enstream);
     if (e->ev_en) hipEventDestroy(e->ev_en);
+    for (hipStream_t x : {e->h2d, e->d2h, e->stream, e->stream2, e->stream3, e->stream4, e->sstream}) if (x) hipStreamDestroy(x);
+    if (e->enstream && e->en_own) hipStreamDestroy(e->enstream);
     delete e;
 }
 
-#define WALLOC(ptr, bytes)                                               \
-    do {                                                                 \
-        int _rc = dalloc((void**)&(ptr), (bytes));                       \
-        if (_rc) { free_work(w); return _rc; }                           \
-    } while (0)
-
 // One Work set: every sorted-order buffer of one batch (sf_internal.h).
-static int alloc_work(sf_engine* e, Work& w) {
+static int work_fill(sf_engine* e, Work& w, DevPool& m) {
     const sf_config& c = e->cfg;
     const size_t N = c.max_batch, R = e->R;
-    WALLOC(w.keys_in, N * 4); WALLOC(w.keys_out, N * 4); WALLOC(w.perm, N * 4);
+    SF_TRY(m.alloc(&w.keys_in, nz(N * 4))); SF_TRY(m.alloc(&w.keys_out, nz(N * 4))); SF_TRY(m.alloc(&w.perm, nz(N * 4)));
     // (12-B payloads when the batch has origins)
-    WALLOC(w.pv_in, N * sizeof(PackedEvO)); WALLOC(w.pv_out, N * sizeof(PackedEvO));
-    WALLOC(w.err, 4);
-    WALLOC(w.head_scan, N * 4);
-    WALLOC(w.seg_start, (N + 1) * 4); WALLOC(w.seg_res, N * 4); WALLOC(w.n_seg, 4);
-    WALLOC(w.s_meta, N * 4);
-    WALLOC(w.s_eref, N * 8); WALLOC(w.s_cts, N * 8);
-    WALLOC(w.s_nargs, N); WALLOC(w.s_atag, N * SF_MAX_ARGS); WALLOC(w.s_abits, N * SF_MAX_ARGS * 8);
-    WALLOC(w.v_status, N); WALLOC(w.v_wait, N * 4); WALLOC(w.v_rule, N * 2);
+    SF_TRY(m.alloc(&w.pv_in, nz(N * sizeof(PackedEvO)))); SF_TRY(m.alloc(&w.pv_out, nz(N * sizeof(PackedEvO))));
+    SF_TRY(m.alloc(&w.err, nz(4)));
+    SF_TRY(m.alloc(&w.head_scan, nz(N * 4)));
+    SF_TRY(m.alloc(&w.seg_start, nz((N + 1) * 4))); SF_TRY(m.alloc(&w.seg_res, nz(N * 4))); SF_TRY(m.alloc(&w.n_seg, nz(4)));
+    SF_TRY(m.alloc(&w.s_meta, nz(N * 4)));
+    SF_TRY(m.alloc(&w.s_eref, nz(N * 8))); SF_TRY(m.alloc(&w.s_cts, nz(N * 8)));
+    SF_TRY(m.alloc(&w.s_nargs, nz(N))); SF_TRY(m.alloc(&w.s_atag, nz(N * SF_MAX_ARGS))); SF_TRY(m.alloc(&w.s_abits, nz(N * SF_MAX_ARGS * 8)));
+    SF_TRY(m.alloc(&w.v_status, nz(N))); SF_TRY(m.alloc(&w.v_wait, nz(N * 4))); SF_TRY(m.alloc(&w.v_rule, nz(N * 2)));
     {
         hipError_t he = query_temp_bytes((uint32_t)N, &w.sort_tmp_bytes, &w.scan_tmp_bytes, &w.pscan_tmp_bytes);
-        if (he != hipSuccess) { free_work(w); return fail(SF_ERR_DEVICE, "scan temp size query"); }
+        if (he != hipSuccess) return fail(SF_ERR_DEVICE, "scan temp size query");
     }
-    WALLOC(w.sort_tmp, w.sort_tmp_bytes);
-    WALLOC(w.scan_tmp, w.scan_tmp_bytes);
-    WALLOC(w.pscan_tmp, w.pscan_tmp_bytes);
+    SF_TRY(m.alloc(&w.sort_tmp, nz(w.sort_tmp_bytes)));
+    SF_TRY(m.alloc(&w.scan_tmp, nz(w.scan_tmp_bytes)));
+    SF_TRY(m.alloc(&w.pscan_tmp, nz(w.pscan_tmp_bytes)));
     // heavy / light split
     w.heavy_min = c.heavy_min_events ? c.heavy_min_events : 512;
     {
@@ -356,7 +302,7 @@ static int alloc_work(sf_engine* e, Work& w) {
     }
     const size_t SC = std::min<size_t>(N, R) + 1;
     w.seg_cap = (uint32_t)SC;
-    WALLOC(w.segflag, SC * 4); WALLOC(w.seg_mode, SC); WALLOC(w.lcounts, 2 * LCLS * 4);
+    SF_TRY(m.alloc(&w.segflag, nz(SC * 4))); SF_TRY(m.alloc(&w.seg_mode, nz(SC))); SF_TRY(m.alloc(&w.lcounts, nz(2 * LCLS * 4)));
     {   // light_list regions per length class: class c holds segments of >= lo_len(c) events
         size_t off = 0;
         for (int k = 0; k < LCLS; k++) {
@@ -366,33 +312,42 @@ static int alloc_work(sf_engine* e, Work& w) {
             w.lcap[k] = (uint32_t)cap;
             off += cap;
         }
-        WALLOC(w.light_list, off * 4);
+        SF_TRY(m.alloc(&w.light_list, nz(off * 4)));
     }
-    WALLOC(w.heavy_list, SC * 4);
-    WALLOC(w.counters, 16 * 4); WALLOC(w.pcg, N * 8); WALLOC(w.segs_lb, segs_lb_bytes((uint32_t)N));
+    SF_TRY(m.alloc(&w.heavy_list, nz(SC * 4)));
+    SF_TRY(m.alloc(&w.counters, nz(16 * 4))); SF_TRY(m.alloc(&w.pcg, nz(N * 8))); SF_TRY(m.alloc(&w.segs_lb, nz(segs_lb_bytes((uint32_t)N))));
     // <= len/TILE + 2 tiles per heavy segment; a ParamFlow-only segment of more
     // than 32 events is heavy too (SM_PARAM, k_classify), whatever heavy_min
     w.fill_tile_cap = (uint32_t)(N / FILL_TILE + 2 * (N / (std::min<uint32_t>(w.heavy_min, 32u) + 1)) + 2);
-    WALLOC(w.fill_tiles, (size_t)2 * w.fill_tile_cap * sizeof(uint2)); WALLOC(w.fill_ntiles, 2 * 4);
+    SF_TRY(m.alloc(&w.fill_tiles, nz((size_t)2 * w.fill_tile_cap * sizeof(uint2)))); SF_TRY(m.alloc(&w.fill_ntiles, nz(2 * 4)));
     w.acc_cap = (uint32_t)std::min<size_t>(std::max<size_t>(N / w.heavy_min * 64, 1 << 16), 1u << 24);
-    WALLOC(w.acc_hw, (size_t)w.acc_cap * ACC_BYTES); WALLOC(w.acc_sec, (size_t)w.acc_cap * ACC_BYTES);
-    WALLOC(w.acc_hw_base, SC * 4); WALLOC(w.acc_sec_base, SC * 4); WALLOC(w.seg_hw0, SC * 8);
-    WALLOC(w.seg_sec0, SC * 8); WALLOC(w.seg_nhw, SC * 4); WALLOC(w.seg_nsec, SC * 4);
-    WALLOC(w.hticks, (N / (w.heavy_min + 1) + 2) * 8);
-    WALLOC(w.sticks, (N / (w.heavy_min + 1) + 2) * 8);
-    WALLOC(w.stream_list, SC * 4);
-    WALLOC(w.xw_list, (N / XW_MIN + 1) * 4);
-    WALLOC(w.passbits, (N / 64 + 2) * 8);
-    WALLOC(w.exit_of, N * 4);
-    WALLOC(w.lxfar, (N / 64 + 2) * 8);
-    WALLOC(w.thr_rec, N * 8);
-    WALLOC(w.tile_rc, (size_t)w.fill_tile_cap * 4); WALLOC(w.seg_rb, SC * 4); WALLOC(w.seg_re, SC * 4);
-    WALLOC(w.vs_cursor, VS_CURSORS(N) * 4);
-    WALLOC(w.s_origin, N * 4); WALLOC(w.s_oslot, N * 4); WALLOC(w.ox_cnt, 8 * 4);
-    WALLOC(w.ox_bflags, (N / OX_TILE + 1) * 4); WALLOC(w.ox_bseg, (N / OX_TILE + 1) * 8);
+    SF_TRY(m.alloc(&w.acc_hw, nz((size_t)w.acc_cap * ACC_BYTES))); SF_TRY(m.alloc(&w.acc_sec, nz((size_t)w.acc_cap * ACC_BYTES)));
+    SF_TRY(m.alloc(&w.acc_hw_base, nz(SC * 4))); SF_TRY(m.alloc(&w.acc_sec_base, nz(SC * 4))); SF_TRY(m.alloc(&w.seg_hw0, nz(SC * 8)));
+    SF_TRY(m.alloc(&w.seg_sec0, nz(SC * 8))); SF_TRY(m.alloc(&w.seg_nhw, nz(SC * 4))); SF_TRY(m.alloc(&w.seg_nsec, nz(SC * 4)));
+    SF_TRY(m.alloc(&w.hticks, nz((N / (w.heavy_min + 1) + 2) * 8)));
+    SF_TRY(m.alloc(&w.sticks, nz((N / (w.heavy_min + 1) + 2) * 8)));
+    SF_TRY(m.alloc(&w.stream_list, nz(SC * 4)));
+    SF_TRY(m.alloc(&w.xw_list, nz((N / XW_MIN + 1) * 4)));
+    SF_TRY(m.alloc(&w.passbits, nz((N / 64 + 2) * 8)));
+    SF_TRY(m.alloc(&w.exit_of, nz(N * 4)));
+    SF_TRY(m.alloc(&w.lxfar, nz((N / 64 + 2) * 8)));
+    SF_TRY(m.alloc(&w.thr_rec, nz(N * 8)));
+    SF_TRY(m.alloc(&w.tile_rc, nz((size_t)w.fill_tile_cap * 4))); SF_TRY(m.alloc(&w.seg_rb, nz(SC * 4))); SF_TRY(m.alloc(&w.seg_re, nz(SC * 4)));
+    SF_TRY(m.alloc(&w.vs_cursor, nz(VS_CURSORS(N) * 4)));
+    SF_TRY(m.alloc(&w.s_origin, nz(N * 4))); SF_TRY(m.alloc(&w.s_oslot, nz(N * 4))); SF_TRY(m.alloc(&w.ox_cnt, nz(8 * 4)));
+    SF_TRY(m.alloc(&w.ox_bflags, nz((N / OX_TILE + 1) * 4))); SF_TRY(m.alloc(&w.ox_bseg, nz((N / OX_TILE + 1) * 8)));
     return SF_OK;
 }
 
+// (the slot is ready only with every buffer of its set; a failure leaves none)
+static int alloc_work(sf_engine* e, Slot& sl) {
+    const int rc = work_fill(e, sl.w, sl.wpool);
+    if (rc) { sl.wpool.clear(); sl.w = Work{}; return rc; }
+    sl.ready = true;
+    return SF_OK;
+}
+
+static int create(sf_engine* e);
 int sf_create(const sf_config* cfg, sf_engine** out) {
     if (!cfg || !out) return fail(SF_ERR_INVALID, "null argument");
     *out = nullptr;
@@ -414,6 +369,14 @@ int sf_create(const sf_config* cfg, sf_engine** out) {
 
     sf_engine* e = new sf_engine();
     e->cfg = c;
+    const int rc = create(e);              // (every failure past this point takes the engine with it)
+    if (rc) { sf_destroy(e); return rc; }
+    *out = e;
+    return SF_OK;
+}
+
+static int create(sf_engine* e) {
+    const sf_config& c = e->cfg;
     e->R = c.max_resources;
     while ((1ull << e->key_bits) < e->R) e->key_bits++;
     {   // stream priorities of the decide phase (SF_STREAM_PRIO, diagnostics):
@@ -447,26 +410,26 @@ int sf_create(const sf_config* cfg, sf_engine** out) {
         else e->side_mode = 0;
     }
     HIP_TRY(hipEventCreateWithFlags(&e->ev_en, hipEventDisableTiming));
-    for (Slot& sl : e->slot) { const int rc = slot_create(sl); if (rc) { sf_destroy(e); return rc; } }
+    for (Slot& sl : e->slot) SF_TRY(slot_create(sl));
 
     DevState& st = e->st;
     st.S = c.sample_count; st.wl = c.interval_ms / c.sample_count; st.interval = c.interval_ms;
     st.occupy_timeout = c.occupy_timeout_ms; st.max_rt = c.statistic_max_rt; st.R = e->R;
     st.shard_count = c.shard_count;
     const size_t R = e->R, S = c.sample_count;
-    DALLOC(st.second, R * S * sizeof(Bucket));
-    DALLOC(st.borrow, R * S * sizeof(Borrow));
-    DALLOC(st.minute, R * MINUTE * sizeof(Bucket));
-    DALLOC(st.threads, R * sizeof(int64_t));
-    DALLOC(st.rule_off, (R + 1) * sizeof(uint32_t));
-    DALLOC(st.prule_off, (R + 1) * sizeof(uint32_t));
-    DALLOC(st.pm_init, R);
-    DALLOC(st.rdesc, R * sizeof(RDesc));
-    DALLOC(st.prio_seen, sizeof(int32_t));
-    DALLOC(st.err, sizeof(int32_t));
+    SF_TRY(e->pool.alloc(&st.second, nz(R * S * sizeof(Bucket))));
+    SF_TRY(e->pool.alloc(&st.borrow, nz(R * S * sizeof(Borrow))));
+    SF_TRY(e->pool.alloc(&st.minute, nz(R * MINUTE * sizeof(Bucket))));
+    SF_TRY(e->pool.alloc(&st.threads, nz(R * sizeof(int64_t))));
+    SF_TRY(e->pool.alloc(&st.rule_off, nz((R + 1) * sizeof(uint32_t))));
+    SF_TRY(e->pool.alloc(&st.prule_off, nz((R + 1) * sizeof(uint32_t))));
+    SF_TRY(e->pool.alloc(&st.pm_init, nz(R)));
+    SF_TRY(e->pool.alloc(&st.rdesc, nz(R * sizeof(RDesc))));
+    SF_TRY(e->pool.alloc(&st.prio_seen, nz(sizeof(int32_t))));
+    SF_TRY(e->pool.alloc(&st.err, nz(sizeof(int32_t))));
     uint64_t pcap = 16;
     while (pcap < (uint64_t)c.param_capacity) pcap <<= 1;
-    DALLOC(st.ptab, pcap * sizeof(ParamSlot));
+    SF_TRY(e->pool.alloc(&st.ptab, nz(pcap * sizeof(ParamSlot))));
     st.pcap_mask = pcap - 1;
     HIP_TRY(hipMemsetAsync((void*)st.rule_off, 0, (R + 1) * sizeof(uint32_t), e->stream));
     HIP_TRY(hipMemsetAsync((void*)st.prule_off, 0, (R + 1) * sizeof(uint32_t), e->stream));
@@ -474,9 +437,9 @@ int sf_create(const sf_config* cfg, sf_engine** out) {
     HIP_TRY(hipMemsetAsync((void*)st.rdesc, 0, R * sizeof(RDesc), e->stream));   // (= no rules)
     HIP_TRY(hipMemsetAsync(st.prio_seen, 0, sizeof(int32_t), e->stream));
     HIP_TRY(hipMemsetAsync(st.ptab, 0, pcap * sizeof(ParamSlot), e->stream));
-    DALLOC(st.pins, 256 * 16 * sizeof(unsigned int));
-    DALLOC(st.xw_stats, 4 * sizeof(unsigned long long));
-    if (hipMemset(e->st.xw_stats, 0, 4 * sizeof(unsigned long long)) != hipSuccess) { sf_destroy(e); return fail(SF_ERR_DEVICE, "memset"); }
+    SF_TRY(e->pool.alloc(&st.pins, nz(256 * 16 * sizeof(unsigned int))));
+    SF_TRY(e->pool.alloc(&st.xw_stats, nz(4 * sizeof(unsigned long long))));
+    HIP_TRY(hipMemset(e->st.xw_stats, 0, 4 * sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(st.pins, 0, 256 * 16 * sizeof(unsigned int), e->stream));
     HIP_TRY(hipMemsetAsync(st.err, 0, sizeof(int32_t), e->stream));
     HIP_TRY(launch_init_state(st, e->stream));
@@ -484,25 +447,20 @@ int sf_create(const sf_config* cfg, sf_engine** out) {
     e->ts.exceed_count = c.exceed_count;
     e->ts.shard_count = c.shard_count; e->ts.shard_index = c.shard_index;
     e->ts.max_occupy_ratio = c.max_occupy_ratio;
-    DALLOC(e->d_sum, sizeof(int64_t));
-    DALLOC(st.last_fetch, R * sizeof(int64_t));
-    DALLOC(st.last_ts, sizeof(int64_t));
+    SF_TRY(e->pool.alloc(&e->d_sum, nz(sizeof(int64_t))));
+    SF_TRY(e->pool.alloc(&st.last_fetch, nz(R * sizeof(int64_t))));
+    SF_TRY(e->pool.alloc(&st.last_ts, nz(sizeof(int64_t))));
     {
         const int64_t t_min = INT64_MIN;
         HIP_TRY(hipMemcpyAsync(st.last_ts, &t_min, 8, hipMemcpyHostToDevice, e->stream));
     }
     HIP_TRY(hipMemsetAsync(st.last_fetch, 0xff, R * sizeof(int64_t), e->stream));   // lastFetchTime = -1
-    DALLOC(e->en, sizeof(EntryNode));
-    DALLOC(e->en_acc, sizeof(EntryAcc));
+    SF_TRY(e->pool.alloc(&e->en, nz(sizeof(EntryNode))));
+    SF_TRY(e->pool.alloc(&e->en_acc, nz(sizeof(EntryAcc))));
     HIP_TRY(launch_entry_init(e->en, st.max_rt, e->stream));
 
-    {
-        const int rc = alloc_work(e, e->slot[0].w);
-        if (rc) { sf_destroy(e); return rc; }
-        e->slot[0].ready = true;
-    }
+    SF_TRY(alloc_work(e, e->slot[0]));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    *out = e;
     return SF_OK;
 }
 
@@ -580,7 +538,7 @@ static int drain(sf_engine* e, bool all = false) {
         if (pk.out_status && !all) { keep |= 1u << k; continue; }
         if (pk.out_status) {
             pk.out_status = nullptr;
-            if (pk.sparse) { const int rc = sparse_complete(pk); if (rc) return rc; }
+            if (pk.sparse) SF_TRY(sparse_complete(pk));
         }
         int32_t err = 0;
         HIP_TRY(hipMemcpy(&err, e->slot[k].w.err, 4, hipMemcpyDeviceToHost));
@@ -601,6 +559,15 @@ static int drain(sf_engine* e, bool all = false) {
 // pool grows by chunks of AX_CHUNK nodes (no node moves) and the index table
 // by rehashing into a larger one, both between batches, so that a batch never
 // fails on their capacity.
+static int chunk_init(sf_engine* e, const AuxChunk& c) {
+    DevState pool = e->st;                     // fresh nodes: the resource-row initialiser on the chunk
+    pool.second = c.sec; pool.borrow = c.bor; pool.minute = c.min; pool.threads = c.thr; pool.R = AX_CHUNK;
+    const hipError_t le = launch_init_state(pool, e->stream);
+    if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("aux init: ") + hipGetErrorString(le));
+    HIP_TRY(hipMemcpyAsync(e->ax_dir + e->ax_host.size(), &c, sizeof c, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SF_OK;
+}
 static int pool_grow(sf_engine* e, uint64_t need) {
     DevState& st = e->st;
     const size_t S = st.S;
@@ -609,15 +576,11 @@ static int pool_grow(sf_engine* e, uint64_t need) {
         if (e->ax_host.size() >= AX_MAX_CHUNKS) return fail(SF_ERR_CAPACITY, "origin / context node pool at its limit");
         const size_t sec_b = (size_t)AX_CHUNK * S * sizeof(Bucket), bor_b = (size_t)AX_CHUNK * S * sizeof(Borrow);
         const size_t min_b = (size_t)AX_CHUNK * MINUTE * sizeof(Bucket), thr_b = (size_t)AX_CHUNK * sizeof(int64_t);
-        char* m = nullptr;
-        HIP_TRY(hipMalloc((void**)&m, sec_b + bor_b + min_b + thr_b));
-        AuxChunk c{(Bucket*)m, (Borrow*)(m + sec_b), (Bucket*)(m + sec_b + bor_b), (int64_t*)(m + sec_b + bor_b + min_b)};
-        DevState pool = st;                    // fresh nodes: the resource-row initialiser on the chunk
-        pool.second = c.sec; pool.borrow = c.bor; pool.minute = c.min; pool.threads = c.thr; pool.R = AX_CHUNK;
-        const hipError_t le = launch_init_state(pool, e->stream);
-        if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("aux init: ") + hipGetErrorString(le));
-        HIP_TRY(hipMemcpyAsync(e->ax_dir + e->ax_host.size(), &c, sizeof c, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
+        char* m = nullptr;                     // (one allocation per chunk)
+        SF_TRY(e->pool.alloc(&m, sec_b + bor_b + min_b + thr_b));
+        const AuxChunk c{(Bucket*)m, (Borrow*)(m + sec_b), (Bucket*)(m + sec_b + bor_b), (int64_t*)(m + sec_b + bor_b + min_b)};
+        const int rc = chunk_init(e, c);
+        if (rc) { e->pool.release(m); return rc; }   // (not yet in the directory)
         e->ax_host.push_back(c);
         st.ax_cap += AX_CHUNK;
     }
@@ -630,20 +593,22 @@ static int pool_grow(sf_engine* e, uint64_t need) {
 // rebuild is retried at twice the size (nothing in flight).
 static int rehash_table(sf_engine* e, const ParamSlot* old, uint64_t old_n, uint64_t ncap,
                         ParamSlot** out, uint64_t* out_cap, const char* what) {
-    if (!e->rh_err) HIP_TRY(hipMalloc((void**)&e->rh_err, sizeof(int32_t)));
-    for (;;) {
+    if (!e->rh_err) SF_TRY(e->pool.alloc(&e->rh_err, sizeof(int32_t)));
+    for (;; ncap *= 2) {
+        DevPool fresh{HIP_MEM};                // (frees the new table on every path but the good one)
         ParamSlot* nt = nullptr;
-        HIP_TRY(hipMalloc((void**)&nt, ncap * sizeof(ParamSlot)));
+        SF_TRY(fresh.alloc(&nt, ncap * sizeof(ParamSlot)));
         HIP_TRY(hipMemsetAsync(nt, 0, ncap * sizeof(ParamSlot), e->stream));
         HIP_TRY(hipMemsetAsync(e->rh_err, 0, sizeof(int32_t), e->stream));
         const hipError_t le = launch_ox_rehash(old, old_n, nt, ncap - 1, e->rh_err, e->stream);
-        if (le != hipSuccess) { hipFree(nt); return fail(SF_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(le)); }
+        if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(le));
         int32_t flag = 0;
         HIP_TRY(hipMemcpyAsync(&flag, e->rh_err, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
-        if (!flag) { *out = nt; *out_cap = ncap; return SF_OK; }
-        HIP_TRY(hipFree(nt));
-        ncap *= 2;
+        if (flag) continue;
+        e->pool.adopt(fresh);
+        *out = nt; *out_cap = ncap;
+        return SF_OK;
     }
 }
 
@@ -653,11 +618,16 @@ static int ensure_aux(sf_engine* e) {
     const uint32_t cap = e->cfg.aux_capacity ? e->cfg.aux_capacity : 65536;
     uint64_t tcap = 16;
     while (tcap < 2ull * cap) tcap <<= 1;
-    HIP_TRY(hipMalloc((void**)&e->ax_dir, AX_MAX_CHUNKS * sizeof(AuxChunk)));
-    HIP_TRY(hipMalloc((void**)&st.ax_count, sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&st.xtab, tcap * sizeof(ParamSlot)));
-    HIP_TRY(hipMemsetAsync(st.ax_count, 0, sizeof(uint32_t), e->stream));
-    HIP_TRY(hipMemsetAsync(st.xtab, 0, tcap * sizeof(ParamSlot), e->stream));
+    // (st.xtab says that the three exist: they reach the engine together or not at all)
+    DevPool fresh{HIP_MEM};
+    AuxChunk* dir = nullptr; uint32_t* count = nullptr; ParamSlot* tab = nullptr;
+    SF_TRY(fresh.alloc(&dir, AX_MAX_CHUNKS * sizeof(AuxChunk)));
+    SF_TRY(fresh.alloc(&count, sizeof(uint32_t)));
+    SF_TRY(fresh.alloc(&tab, tcap * sizeof(ParamSlot)));
+    HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint32_t), e->stream));
+    HIP_TRY(hipMemsetAsync(tab, 0, tcap * sizeof(ParamSlot), e->stream));
+    e->pool.adopt(fresh);
+    e->ax_dir = dir; st.ax_count = count; st.xtab = tab;
     st.xcap_mask = tcap - 1;
     st.ax_chunks = e->ax_dir;
     st.ax_cap = 0;
@@ -671,27 +641,40 @@ static int index_grow(sf_engine* e, uint64_t need) {
     while (tcap < 2 * need) tcap <<= 1;
     ParamSlot* nt = nullptr;
     HIP_TRY(hipDeviceSynchronize());
-    { const int rc = rehash_table(e, st.xtab, st.xcap_mask + 1, tcap, &nt, &tcap, "index rehash"); if (rc) return rc; }
-    HIP_TRY(hipFree(st.xtab));
+    SF_TRY(rehash_table(e, st.xtab, st.xcap_mask + 1, tcap, &nt, &tcap, "index rehash"));
+    e->pool.release(st.xtab);
     st.xtab = nt;
     st.xcap_mask = tcap - 1;
     e->aux_grows++;
     return SF_OK;
 }
 
-// per-Work-set maps of the origin pass sized for the index table (every pool
-// slot is below its capacity), the slot -> heavy id map reset to XNONE
-static int ox_maps(sf_engine* e, Work& w, bool reset, hipStream_t ss) {
+// The origin pass's three maps of a Work set (pool slot -> heavy id, heavy id
+// -> slot, thread deltas): built in a scratch pool, installed together.
+struct OxMaps { uint32_t* hmap = nullptr; uint32_t* hslot = nullptr; int64_t* thr = nullptr; };
+static int ox_map_alloc(DevPool& fresh, size_t need, OxMaps& m) {
+    SF_TRY(fresh.alloc(&m.hmap, need * 4));
+    SF_TRY(fresh.alloc(&m.hslot, need * 4));
+    return fresh.alloc(&m.thr, need * 8);
+}
+static void ox_map_install(Slot& sl, DevPool& fresh, const OxMaps& m, size_t n) {
+    Work& w = sl.w;
+    sl.wpool.release_all(w.ox_hmap, w.ox_hslot, w.ox_thr);
+    sl.wpool.adopt(fresh);
+    w.ox_hmap = m.hmap; w.ox_hslot = m.hslot; w.ox_thr = m.thr; w.ox_hmap_n = w.ox_hslot_n = n;
+}
+// the maps sized for the index table (every pool slot is below its
+// capacity), the slot -> heavy id map reset to XNONE
+static int ox_maps(sf_engine* e, Slot& sl, bool reset, hipStream_t ss) {
+    Work& w = sl.w;
     const size_t need = (size_t)e->st.xcap_mask + 1;
     if (w.ox_hmap_n < need) {
-        if (w.ox_hmap) hipFree(w.ox_hmap);
-        if (w.ox_hslot) hipFree(w.ox_hslot);
-        if (w.ox_thr) hipFree(w.ox_thr);
-        w.ox_hmap = nullptr; w.ox_hslot = nullptr; w.ox_thr = nullptr; w.ox_hmap_n = w.ox_hslot_n = 0;
-        HIP_TRY(hipMalloc((void**)&w.ox_hmap, need * 4));
-        HIP_TRY(hipMalloc((void**)&w.ox_hslot, need * 4));
-        HIP_TRY(hipMalloc((void**)&w.ox_thr, need * 8));
-        w.ox_hmap_n = w.ox_hslot_n = need;
+        sl.wpool.release_all(w.ox_hmap, w.ox_hslot, w.ox_thr);      // (nothing to keep: freed first)
+        w.ox_hmap_n = w.ox_hslot_n = 0;
+        DevPool fresh{HIP_MEM};
+        OxMaps m;
+        SF_TRY(ox_map_alloc(fresh, need, m));
+        ox_map_install(sl, fresh, m, need);
         reset = true;
     }
     if (reset) HIP_TRY(hipMemsetAsync(w.ox_hmap, 0xff, w.ox_hmap_n * 4, ss));
@@ -704,14 +687,16 @@ static int ox_maps(sf_engine* e, Work& w, bool reset, hipStream_t ss) {
 // the new slots -- all before the decide phase, so nothing is ever dropped.
 // The host waits for the sort stream here (the previous batch's decide phase
 // keeps running).  Fills `plan` for the origin-node pass of the decide phase.
-static int ox_prologue(sf_engine* e, Work& w, const DevBatch& b, hipStream_t ss) {
-    { const int rc = ensure_aux(e); if (rc) return rc; }
+static int ox_prologue(sf_engine* e, Slot& sl, const DevBatch& b, hipStream_t ss) {
+    Work& w = sl.w;
+    SF_TRY(ensure_aux(e));
     // a batch that stopped between its index pass and its origin apply (an
     // early error return) left its heavy ids in ox_hmap: reset them
-    { const int rc = ox_maps(e, w, w.ox_dirty, ss); if (rc) return rc; }
-    if (b.origin && !w.ox_pairs) {                 // (at most one pair per event)
-        HIP_TRY(hipMalloc((void**)&w.ox_pairs, (size_t)e->cfg.max_batch * sizeof(uint4)));
-        HIP_TRY(hipMalloc((void**)&w.ox_plist, (size_t)e->cfg.max_batch * sizeof(uint32_t)));
+    SF_TRY(ox_maps(e, sl, w.ox_dirty, ss));
+    if (b.origin && !w.ox_pairs_cap) {             // (at most one pair per event)
+        SF_TRY(sl.wpool.alloc(&w.ox_pairs, (size_t)e->cfg.max_batch * sizeof(uint4)));
+        const int rc = sl.wpool.alloc(&w.ox_plist, (size_t)e->cfg.max_batch * sizeof(uint32_t));
+        if (rc) { sl.wpool.release(w.ox_pairs); return rc; }
         w.ox_pairs_cap = e->cfg.max_batch;
     }
     return SF_OK;
@@ -730,27 +715,26 @@ static int ox_launch_index(sf_engine* e, Work& w, const DevBatch& b, hipStream_t
 }
 // after the index passes (counts read): the pool covers every slot, the index
 // stays at most half full, the plan of the origin-node pass
-static int ox_plan(sf_engine* e, Work& w, const uint32_t* cnt, uint32_t ax, const int64_t* t01, OxPlan* plan) {
-    { const int rc = pool_grow(e, ax); if (rc) return rc; }
+static int ox_plan(sf_engine* e, Slot& sl, const uint32_t* cnt, uint32_t ax, const int64_t* t01, OxPlan* plan) {
+    Work& w = sl.w;
+    SF_TRY(pool_grow(e, ax));
     // keep the index at most half full for the next batches
     if ((uint64_t)ax * 2 > e->st.xcap_mask + 1) {
         HIP_TRY(hipDeviceSynchronize());
         // (the Work set's hmap entries of this batch are slot-indexed: still valid after a rehash)
         const size_t old_n = w.ox_hmap_n;
-        { const int rc = index_grow(e, (uint64_t)ax * 2); if (rc) return rc; }
+        SF_TRY(index_grow(e, (uint64_t)ax * 2));
         if (w.ox_hmap_n < (size_t)e->st.xcap_mask + 1) {
             // regrow the maps keeping this batch's heavy ids
-            uint32_t* nh = nullptr; uint32_t* ns = nullptr; int64_t* nt = nullptr;
             const size_t need = (size_t)e->st.xcap_mask + 1;
-            HIP_TRY(hipMalloc((void**)&nh, need * 4));
-            HIP_TRY(hipMalloc((void**)&ns, need * 4));
-            HIP_TRY(hipMalloc((void**)&nt, need * 8));
-            HIP_TRY(hipMemsetAsync(nh, 0xff, need * 4, e->stream));
-            HIP_TRY(hipMemcpyAsync(nh, w.ox_hmap, old_n * 4, hipMemcpyDeviceToDevice, e->stream));
-            HIP_TRY(hipMemcpyAsync(ns, w.ox_hslot, old_n * 4, hipMemcpyDeviceToDevice, e->stream));
+            DevPool fresh{HIP_MEM};            // (the new maps, freed by an early return)
+            OxMaps m;
+            SF_TRY(ox_map_alloc(fresh, need, m));
+            HIP_TRY(hipMemsetAsync(m.hmap, 0xff, need * 4, e->stream));
+            HIP_TRY(hipMemcpyAsync(m.hmap, w.ox_hmap, old_n * 4, hipMemcpyDeviceToDevice, e->stream));
+            HIP_TRY(hipMemcpyAsync(m.hslot, w.ox_hslot, old_n * 4, hipMemcpyDeviceToDevice, e->stream));
             HIP_TRY(hipStreamSynchronize(e->stream));
-            hipFree(w.ox_hmap); hipFree(w.ox_hslot); hipFree(w.ox_thr);
-            w.ox_hmap = nh; w.ox_hslot = ns; w.ox_thr = nt; w.ox_hmap_n = w.ox_hslot_n = need;
+            ox_map_install(sl, fresh, m, need);
         }
     }
     plan->n_heavy = cnt[OXC_HEAVY];
@@ -761,20 +745,21 @@ static int ox_plan(sf_engine* e, Work& w, const uint32_t* cnt, uint32_t ax, cons
     plan->win.wm = (uint32_t)(t01[1] / 1000 - plan->win.w0m + 1);
     const size_t acc_n = (size_t)plan->n_heavy * ((size_t)plan->win.ws + plan->win.wm);
     if (w.ox_acc_n < acc_n) {
-        if (w.ox_acc) hipFree(w.ox_acc);
-        w.ox_acc = nullptr; w.ox_acc_n = 0;
+        sl.wpool.release(w.ox_acc);
+        w.ox_acc_n = 0;
         const size_t n2 = acc_n + acc_n / 4;
-        HIP_TRY(hipMalloc(&w.ox_acc, n2 * sizeof(OxAcc)));
+        SF_TRY(sl.wpool.alloc(&w.ox_acc, n2 * sizeof(OxAcc)));
         w.ox_acc_n = n2;
     }
     return SF_OK;
 }
-static int prepare_origins(sf_engine* e, Work& w, const DevBatch& b, hipStream_t ss, OxPlan* plan) {
-    { const int rc = ox_prologue(e, w, b, ss); if (rc) return rc; }
+static int prepare_origins(sf_engine* e, Slot& sl, const DevBatch& b, hipStream_t ss, OxPlan* plan) {
+    Work& w = sl.w;
+    SF_TRY(ox_prologue(e, sl, b, ss));
     uint32_t cnt[8] = {0};
     uint32_t ax = 0;
     for (int round = 0;; round++) {
-        { const int rc = ox_launch_index(e, w, b, ss); if (rc) return rc; }
+        SF_TRY(ox_launch_index(e, w, b, ss));
         HIP_TRY(hipMemcpyAsync(cnt, w.ox_cnt, sizeof cnt, hipMemcpyDeviceToHost, ss));
         HIP_TRY(hipMemcpyAsync(&ax, e->st.ax_count, 4, hipMemcpyDeviceToHost, ss));
         HIP_TRY(hipStreamSynchronize(ss));
@@ -784,21 +769,21 @@ static int prepare_origins(sf_engine* e, Work& w, const DevBatch& b, hipStream_t
         // reserved (every absent key counted, by each workgroup that missed it),
         // the pass runs again
         HIP_TRY(hipDeviceSynchronize());
-        { const int rc = index_grow(e, std::max<uint64_t>((uint64_t)cnt[OXC_RESERVED], ax) * 3 / 2); if (rc) return rc; }
-        { const int rc = ox_maps(e, w, true, ss); if (rc) return rc; }
+        SF_TRY(index_grow(e, std::max<uint64_t>((uint64_t)cnt[OXC_RESERVED], ax) * 3 / 2));
+        SF_TRY(ox_maps(e, sl, true, ss));
     }
     int64_t t01[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(&t01[0], b.ts, 8, hipMemcpyDeviceToHost, ss));
     HIP_TRY(hipMemcpyAsync(&t01[1], b.ts + (b.n - 1), 8, hipMemcpyDeviceToHost, ss));
     HIP_TRY(hipStreamSynchronize(ss));
-    return ox_plan(e, w, cnt, ax, t01, plan);
+    return ox_plan(e, sl, cnt, ax, t01, plan);
 }
 
 
 int sf_load_flow_rules(sf_engine* e, const sf_flow_rule* rules, uint32_t n) {
     if (!e || (n && !rules)) return fail(SF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(e->mu);
-    { const int rc = drain(e); if (rc) return rc; }   // pending batches were sorted under the old rules
+    SF_TRY(drain(e));   // pending batches were sorted under the old rules
     std::vector<uint32_t> counts(e->R + 1, 0);
     std::vector<const sf_flow_rule*> valid;
     std::vector<uint32_t> valid_local, valid_ref;
@@ -843,14 +828,13 @@ int sf_load_flow_rules(sf_engine* e, const sf_flow_rule* rules, uint32_t n) {
     std::vector<uint32_t> xmap;
     const bool xflow = build_xmap(dr.data(), off.data(), e->R, xmap);
     if (xflow) {
-        const int rc = ensure_aux(e);
-        if (rc) return rc;
-        if (!e->xmap_buf) HIP_TRY(hipMalloc((void**)&e->xmap_buf, (size_t)e->R * sizeof(uint32_t)));
+        SF_TRY(ensure_aux(e));
+        if (!e->xmap_buf) SF_TRY(e->pool.alloc(&e->xmap_buf, (size_t)e->R * sizeof(uint32_t)));
         HIP_TRY(hipMemcpyAsync(e->xmap_buf, xmap.data(), (size_t)e->R * sizeof(uint32_t), hipMemcpyHostToDevice,
                                e->stream));
         std::vector<uint8_t> xw;
         build_xw(dr.data(), off.data(), e->R, xmap, xw);
-        if (!e->xw_buf) HIP_TRY(hipMalloc((void**)&e->xw_buf, (size_t)e->R));
+        if (!e->xw_buf) SF_TRY(e->pool.alloc(&e->xw_buf, (size_t)e->R));
         HIP_TRY(hipMemcpyAsync(e->xw_buf, xw.data(), (size_t)e->R, hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
     }
@@ -863,10 +847,9 @@ int sf_load_flow_rules(sf_engine* e, const sf_flow_rule* rules, uint32_t n) {
         }
         e->st.n_stream_rules = ns; e->st.n_window_rules = nw;
     }
-    if (e->st.rules) { hipFree((void*)e->st.rules); e->st.rules = nullptr; }
-    if (e->st.rstate) { hipFree(e->st.rstate); e->st.rstate = nullptr; }
-    HIP_TRY(hipMalloc((void**)&e->st.rules, std::max<size_t>(1, dr.size()) * sizeof(DevRule)));
-    HIP_TRY(hipMalloc((void**)&e->st.rstate, std::max<size_t>(1, ds.size()) * sizeof(DevRuleState)));
+    e->pool.release_all(e->st.rules, e->st.rstate);
+    SF_TRY(e->pool.alloc(&e->st.rules, std::max<size_t>(1, dr.size()) * sizeof(DevRule)));
+    SF_TRY(e->pool.alloc(&e->st.rstate, std::max<size_t>(1, ds.size()) * sizeof(DevRuleState)));
     if (!dr.empty()) {
         HIP_TRY(hipMemcpyAsync((void*)e->st.rules, dr.data(), dr.size() * sizeof(DevRule), hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(e->st.rstate, ds.data(), ds.size() * sizeof(DevRuleState), hipMemcpyHostToDevice, e->stream));
@@ -887,7 +870,7 @@ int sf_load_param_rules(sf_engine* e, const sf_param_rule* rules, uint32_t n, co
                         uint32_t n_items) {
     if (!e || (n && !rules) || (n_items && !items)) return fail(SF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(e->mu);
-    { const int rc = drain(e); if (rc) return rc; }   // pending batches were sorted under the old rules
+    SF_TRY(drain(e));   // pending batches were sorted under the old rules
     std::vector<uint32_t> counts(e->R + 1, 0), loc(n);
     for (uint32_t i = 0; i < n; i++) {
         if (!local_of(e, rules[i].resource, &loc[i])) return fail(SF_ERR_INVALID, "rule resource outside this shard");
@@ -908,10 +891,9 @@ int sf_load_param_rules(sf_engine* e, const sf_param_rule* rules, uint32_t n, co
     for (uint32_t i = 0; i < n_items; i++) { di[i].bits = items[i].bits; di[i].count = items[i].count; di[i].tag = items[i].tag; }
     e->n_prule = n;
     e->st.n_prule = n;
-    if (e->st.prules) { hipFree(e->st.prules); e->st.prules = nullptr; }
-    if (e->st.items) { hipFree((void*)e->st.items); e->st.items = nullptr; }
-    HIP_TRY(hipMalloc((void**)&e->st.prules, std::max<size_t>(1, dp.size()) * sizeof(DevParamRule)));
-    HIP_TRY(hipMalloc((void**)&e->st.items, std::max<size_t>(1, di.size()) * sizeof(DevHotItem)));
+    e->pool.release_all(e->st.prules, e->st.items);
+    SF_TRY(e->pool.alloc(&e->st.prules, std::max<size_t>(1, dp.size()) * sizeof(DevParamRule)));
+    SF_TRY(e->pool.alloc(&e->st.items, std::max<size_t>(1, di.size()) * sizeof(DevHotItem)));
     if (n) HIP_TRY(hipMemcpyAsync(e->st.prules, dp.data(), dp.size() * sizeof(DevParamRule), hipMemcpyHostToDevice, e->stream));
     if (n_items) HIP_TRY(hipMemcpyAsync((void*)e->st.items, di.data(), di.size() * sizeof(DevHotItem), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync((void*)e->st.prule_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, e->stream));
@@ -936,7 +918,7 @@ int sf_load_param_rules(sf_engine* e, const sf_param_rule* rules, uint32_t n, co
 int sf_load_system_rules(sf_engine* e, const sf_system_rule* rules, uint32_t n) {
     if (!e || (n && !rules)) return fail(SF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(e->mu);
-    { const int rc = drain(e); if (rc) return rc; }
+    SF_TRY(drain(e));
     SysRule r{};
     r.qps = r.highest_load = r.highest_cpu = 1.7976931348623157e308;
     r.max_rt = r.max_thread = INT64_MAX;
@@ -963,8 +945,6 @@ int sf_set_system_status(sf_engine* e, double avg_load, double cpu_usage) {
     e->sys.cur_load = avg_load; e->sys.cur_cpu = cpu_usage;
     return SF_OK;
 }
-
-static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The exact ParamFlow table never fills during a batch: before a batch with
 // ParamFlow rules, the keys it can insert at most ((events + collection
@@ -995,15 +975,15 @@ static int param_reserve(sf_engine* e, uint64_t bound) {
         if (idle && sl.used && hipEventQuery(sl.done) != hipSuccess) idle = false;
     if (idle) {
         uint64_t used = 0;
-        { const int rc = read_used(&used); if (rc) return rc; }
+        SF_TRY(read_used(&used));
         e->p_used = used;
         e->p_pending = 0;
         if ((used + bound) * 2 <= cap) { e->p_pending = bound; return SF_OK; }
     }
-    { const int rc = drain(e); if (rc) return rc; }
+    SF_TRY(drain(e));
     HIP_TRY(hipStreamSynchronize(e->stream));
     uint64_t used = 0;
-    { const int rc = read_used(&used); if (rc) return rc; }
+    SF_TRY(read_used(&used));
     e->p_used = used;
     e->p_pending = 0;
     if ((used + bound) * 2 > cap) {
@@ -1011,8 +991,8 @@ static int param_reserve(sf_engine* e, uint64_t bound) {
         while ((used + bound) * 2 > ncap) ncap <<= 1;
         ParamSlot* nt = nullptr;
         HIP_TRY(hipDeviceSynchronize());
-        { const int rc = rehash_table(e, e->st.ptab, cap, ncap, &nt, &ncap, "param rehash"); if (rc) return rc; }
-        HIP_TRY(hipFree(e->st.ptab));
+        SF_TRY(rehash_table(e, e->st.ptab, cap, ncap, &nt, &ncap, "param rehash"));
+        e->pool.release(e->st.ptab);
         e->st.ptab = nt;
         e->st.pcap_mask = ncap - 1;
         e->p_grows++;
@@ -1029,29 +1009,18 @@ static int stage_batch(sf_engine* e, const sf_event_batch* in, const sf_verdicts
     const uint32_t n = in->n;
     b.n = n; b.arg_slots = in->arg_slots; b.arg_stride = n;
     if (in->mem == SF_MEM_HOST) {
-        size_t need = 0;
-        size_t o_res = need; need += align_up((size_t)n * 4);
-        size_t o_ts = need; need += align_up((size_t)n * 8);
-        size_t o_cnt = need; need += align_up((size_t)n * 4);
-        size_t o_fl = need; need += align_up((size_t)n);
-        size_t o_er = need; need += in->entry_ref ? align_up((size_t)n * 8) : 0;
-        size_t o_ct = need; need += (in->entry_ref && in->create_ts) ? align_up((size_t)n * 8) : 0;
-        size_t o_na = need; need += in->n_args ? align_up((size_t)n) : 0;
-        size_t o_at = need; need += align_up((size_t)n * in->arg_slots);
-        size_t o_ab = need; need += align_up((size_t)n * in->arg_slots * 8);
+        Layout L;
         const bool coll = in->arg_elem_off != nullptr;
-        size_t o_eo = need; need += coll ? align_up(((size_t)n * in->arg_slots + 1) * 4) : 0;
-        size_t o_et = need; need += coll ? align_up((size_t)in->n_elems) : 0;
-        size_t o_eb = need; need += coll ? align_up((size_t)in->n_elems * 8) : 0;
-        size_t o_og = need; need += in->origin ? align_up((size_t)n * 4) : 0;
-        size_t o_cx = need; need += in->context ? align_up((size_t)n * 4) : 0;
-        if (need > e->stage_in_bytes) {
-            if (e->stage_in) hipFree(e->stage_in);
-            e->stage_in = nullptr;
-            HIP_TRY(hipMalloc(&e->stage_in, need));
-            e->stage_in_bytes = need;
-        }
-        char* base = (char*)e->stage_in;
+        const size_t o_res = L.take((size_t)n * 4), o_ts = L.take((size_t)n * 8), o_cnt = L.take((size_t)n * 4);
+        const size_t o_fl = L.take(n), o_er = L.take_if(in->entry_ref, (size_t)n * 8);
+        const size_t o_ct = L.take_if(in->entry_ref && in->create_ts, (size_t)n * 8), o_na = L.take_if(in->n_args, n);
+        // (the argument arrays have their room with or without arguments)
+        const size_t o_at = L.take((size_t)n * in->arg_slots), o_ab = L.take((size_t)n * in->arg_slots * 8);
+        const size_t o_eo = L.take_if(coll, ((size_t)n * in->arg_slots + 1) * 4), o_et = L.take_if(coll, in->n_elems);
+        const size_t o_eb = L.take_if(coll, (size_t)in->n_elems * 8), o_og = L.take_if(in->origin, (size_t)n * 4);
+        const size_t o_cx = L.take_if(in->context, (size_t)n * 4);
+        SF_TRY(e->stage_in.reserve(e->pool, L.size()));
+        char* base = e->stage_in.at(0);
         auto up = [&](size_t off, const void* src, size_t bytes) -> const void* {
             if (!src || !bytes) return nullptr;
             hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, ss);
@@ -1081,17 +1050,13 @@ static int stage_batch(sf_engine* e, const sf_event_batch* in, const sf_verdicts
         b.origin = in->origin; b.ctx = in->context;
     }
     if (out->mem == SF_MEM_HOST) {
-        size_t need = align_up((size_t)n) + align_up((size_t)n * 4) + align_up((size_t)n * 2);
-        if (need > e->stage_out_bytes) {
-            if (e->stage_out) hipFree(e->stage_out);
-            e->stage_out = nullptr;
-            HIP_TRY(hipMalloc(&e->stage_out, need));
-            e->stage_out_bytes = need;
-        }
-        char* base = (char*)e->stage_out;
-        dv.status = (uint8_t*)base;
-        dv.wait = out->wait_ms ? (int32_t*)(base + align_up(n)) : nullptr;
-        dv.rule = out->rule_idx ? (uint16_t*)(base + align_up(n) + align_up((size_t)n * 4)) : nullptr;
+        Layout L;
+        const size_t o_st = L.take(n), o_wt = L.take((size_t)n * 4), o_ru = L.take((size_t)n * 2);
+        SF_TRY(e->stage_out.reserve(e->pool, L.size()));
+        char* base = e->stage_out.at(0);
+        dv.status = (uint8_t*)(base + o_st);
+        dv.wait = out->wait_ms ? (int32_t*)(base + o_wt) : nullptr;
+        dv.rule = out->rule_idx ? (uint16_t*)(base + o_ru) : nullptr;
     } else {
         dv.status = out->status; dv.wait = out->wait_ms; dv.rule = out->rule_idx;
     }
@@ -1114,8 +1079,7 @@ static int check_event_batch(const sf_engine* e, const sf_event_batch* in) {
 // ParamFlow table for every key the batch can insert.
 static int reserve_for_batch(sf_engine* e, const sf_event_batch* in, bool with_ox, uint32_t n_arg_events) {
     if (with_ox && !e->st.xtab) {
-        const int rc = ensure_aux(e);
-        if (rc) return rc;
+        SF_TRY(ensure_aux(e));
         HIP_TRY(hipStreamSynchronize(e->stream));
     }
     const uint64_t elems = in->arg_elem_off ? in->n_elems : 0;
@@ -1134,10 +1098,11 @@ static int take_slot(sf_engine* e, Slot& sl) {
 
 // the SystemRule planner's buffers and its verdicts (sf_system.h), on first use
 static int sys_buffers_ensure(sf_engine* e) {
-    if (!e->sys_plan) HIP_TRY(hipMalloc((void**)&e->sys_plan, sizeof(SysPlanDev)));
-    if (!e->sys_pa) HIP_TRY(hipMalloc((void**)&e->sys_pa, SYS_PLAN_BLOCKS * sizeof(SysExitQ)));
-    if (!e->sys_pb) HIP_TRY(hipMalloc((void**)&e->sys_pb, SYS_PLAN_BLOCKS * sizeof(SysEntQ)));
-    if (!e->sys_mask) HIP_TRY(hipMalloc((void**)&e->sys_mask, e->cfg.max_batch));
+    // (each on its own: one that is missing after a failure is allocated by the next call)
+    if (!e->sys_plan) SF_TRY(e->pool.alloc(&e->sys_plan, sizeof(SysPlanDev)));
+    if (!e->sys_pa) SF_TRY(e->pool.alloc(&e->sys_pa, SYS_PLAN_BLOCKS * sizeof(SysExitQ)));
+    if (!e->sys_pb) SF_TRY(e->pool.alloc(&e->sys_pb, SYS_PLAN_BLOCKS * sizeof(SysEntQ)));
+    if (!e->sys_mask) SF_TRY(e->pool.alloc(&e->sys_mask, e->cfg.max_batch));
     return SF_OK;
 }
 
@@ -1196,8 +1161,7 @@ static int decide_view(sf_engine* e, Slot& sl, DevState& stl, const DevBatch& b,
     hipError_t le = launch_sort(stl, w, v, e->cfg.shard_count, e->cfg.shard_index, e->key_bits, s, sl.evs, false);
     OxPlan plan{};
     if (le == hipSuccess && with_ox) {
-        const int rc = prepare_origins(e, w, v, s, &plan);
-        if (rc) return rc;
+        SF_TRY(prepare_origins(e, sl, v, s, &plan));
         stl.xtab = e->st.xtab; stl.xcap_mask = e->st.xcap_mask; stl.ax_cap = e->st.ax_cap;
     }
     if (le == hipSuccess)
@@ -1226,8 +1190,8 @@ static int submit_sys_rounds(sf_engine* e, Slot& sl, const DevBatch& b, const De
     const uint32_t n = b.n;
     hipStream_t s = e->stream, ss = e->serial ? e->stream : e->sstream;
     Work& w = sl.w;
-    { const int rc = sys_buffers_ensure(e); if (rc) return rc; }
-    if (!e->sys_ibuf && e->st.n_prule) HIP_TRY(hipMalloc((void**)&e->sys_ibuf, SYS_PLAN_CAP));
+    SF_TRY(sys_buffers_ensure(e));
+    if (!e->sys_ibuf && e->st.n_prule) SF_TRY(e->pool.alloc(&e->sys_ibuf, SYS_PLAN_CAP));
     HIP_TRY(hipMemsetAsync(w.err, 0, sizeof(int32_t), ss));
     if (pre) {
         const hipError_t pe = (*pre)(ss, w.err);
@@ -1235,7 +1199,7 @@ static int submit_sys_rounds(sf_engine* e, Slot& sl, const DevBatch& b, const De
     }
     HIP_TRY(hipEventRecord(sl.sorted, ss));
     HIP_TRY(hipStreamWaitEvent(s, sl.sorted, 0));
-    { const int rc = en_fence(e); if (rc) return rc; }
+    SF_TRY(en_fence(e));
     DevState stl = e->st;
     stl.err = w.err;
     uint32_t p = 0, rounds = 0;
@@ -1251,7 +1215,7 @@ static int submit_sys_rounds(sf_engine* e, Slot& sl, const DevBatch& b, const De
         if (q <= p || q > n) return fail(SF_ERR_DEVICE, "system planner made no progress");
         DevBatch v;
         DevVerdicts dvv;
-        { const int rc = decide_view(e, sl, stl, b, dv, p, q, with_ox, v, dvv); if (rc) return rc; }
+        SF_TRY(decide_view(e, sl, stl, b, dv, p, q, with_ox, v, dvv));
         // the system verdicts of the inert entries (ENTRY_NODE is still at p)
         if (qi[1]) le = sys_plan_fix(stl, b, dv, e->sys_mask, e->sys, p, q, e->sys_plan, e->sys_pa, e->sys_pb, s);
         if (le == hipSuccess) le = launch_entry_node(stl, v, dvv.status, e->en, e->en_acc, s);
@@ -1267,7 +1231,7 @@ static int submit_core(sf_engine* e, const sf_event_batch* in, sf_verdicts* out,
                        const uint8_t* forced = nullptr, const PackedHook* hook = nullptr) {
     if (!e || !in || !out || !out->status) return fail(SF_ERR_INVALID, "null argument");
     if (in->n == 0) return SF_OK;
-    { const int rc = check_event_batch(e, in); if (rc) return rc; }
+    SF_TRY(check_event_batch(e, in));
     // SystemRules read the node-wide ENTRY_NODE: a sharded engine decides them
     // only through the round protocol (sf_system_plan / sf_submit_forced)
     if (e->sys.check && e->cfg.shard_count > 1 && !forced)
@@ -1281,25 +1245,24 @@ static int submit_core(sf_engine* e, const sf_event_batch* in, sf_verdicts* out,
     // asynchronous only for HBM-resident batches and verdicts, without SystemRules
     async = async && in->mem != SF_MEM_HOST && out->mem != SF_MEM_HOST && !e->sys.check && !forced;
     // (the first batch with origins builds the origin-node pool with nothing in flight)
-    if (!async || (with_ox && !e->st.xtab)) { const int rc = drain(e); if (rc) return rc; }
-    { const int rc = reserve_for_batch(e, in, with_ox, hook ? hook->n_arg_events : in->n); if (rc) return rc; }
+    if (!async || (with_ox && !e->st.xtab)) SF_TRY(drain(e));
+    SF_TRY(reserve_for_batch(e, in, with_ox, hook ? hook->n_arg_events : in->n));
     const PreSort* pre = hook ? &hook->pre : nullptr;
     for (Slot& x : e->slot) {                      // the other Work sets on first asynchronous use
         if (!async || x.ready) continue;
         HIP_TRY(hipStreamSynchronize(s));
-        { const int rc = alloc_work(e, x.w); if (rc) return rc; }
-        x.ready = true;
+        SF_TRY(alloc_work(e, x));
     }
     Slot& sl = e->slot[e->cur];
-    { const int rc = take_slot(e, sl); if (rc) return rc; }
+    SF_TRY(take_slot(e, sl));
     Work& w = sl.w;
     DevBatch b{};
     DevVerdicts dv{};
-    { const int rc = stage_batch(e, in, out, ss, b, dv); if (rc) return rc; }
+    SF_TRY(stage_batch(e, in, out, ss, b, dv));
     b.acsr = hook && hook->acsr;
     if (forced) {
         // the forced SystemRule verdicts of this (sub-)batch, planned node-wide
-        { const int rc = sys_buffers_ensure(e); if (rc) return rc; }
+        SF_TRY(sys_buffers_ensure(e));
         HIP_TRY(hipMemcpyAsync(e->sys_mask, forced, n, hipMemcpyHostToDevice, ss));
         b.sys = e->sys_mask;
     }
@@ -1318,8 +1281,7 @@ static int submit_core(sf_engine* e, const sf_event_batch* in, sf_verdicts* out,
     if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("launch: ") + hipGetErrorString(le));
     OxPlan plan{};
     if (with_ox) {
-        const int rc = prepare_origins(e, w, b, ss, &plan);
-        if (rc) return rc;
+        SF_TRY(prepare_origins(e, sl, b, ss, &plan));
         stl.xtab = e->st.xtab; stl.xcap_mask = e->st.xcap_mask; stl.ax_cap = e->st.ax_cap;
     }
     HIP_TRY(hipEventRecord(sl.sorted, ss));
@@ -1336,7 +1298,7 @@ static int submit_core(sf_engine* e, const sf_event_batch* in, sf_verdicts* out,
     // ENTRY_NODE: every IN event's StatisticSlot updates (after the verdicts, stream
     // order); under the round protocol the node-wide stream updates it (sf_entry_node_add)
     if (!side && !forced) {
-        { const int rc = en_fence(e); if (rc) return rc; }
+        SF_TRY(en_fence(e));
         le = launch_entry_node(stl, b, dv.status, e->en, e->en_acc, s);
         if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("entry node: ") + hipGetErrorString(le));
     }
@@ -1387,6 +1349,17 @@ static int sparse_complete(PkStage& pk) {
     return SF_OK;
 }
 
+// Before a buffer of the slot's packed stage is reallocated -- the only time
+// the host blocks for it -- every batch that may still read or write it is
+// done: the slot's last batch, its expansion, the copy of its verdicts.
+static int pk_quiesce(Slot& sl) {
+    PkStage& pk = sl.pk;
+    if (sl.used) HIP_TRY(hipEventSynchronize(sl.end));
+    if (pk.consumed_pending) { HIP_TRY(hipEventSynchronize(pk.consumed)); pk.consumed_pending = false; }
+    if (pk.d2h_pending) { HIP_TRY(hipEventSynchronize(pk.d2h)); pk.d2h_pending = false; }
+    return SF_OK;
+}
+
 static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* out, bool async,
                          const sf_sparse_verdicts* sp = nullptr) {
     if (!e || !in || !out || !out->status) return fail(SF_ERR_INVALID, "null argument");
@@ -1418,14 +1391,14 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
             HIP_TRY(hipEventCreateWithFlags(&p.h2d, hipEventDisableTiming));
             HIP_TRY(hipEventCreateWithFlags(&p.d2h, hipEventDisableTiming));
             HIP_TRY(hipEventCreateWithFlags(&p.consumed, hipEventDisableTiming));
-            HIP_TRY(hipHostMalloc((void**)&p.err_host, 4, hipHostMallocDefault));
+            SF_TRY(x.pkpool.alloc_host(&p.err_host, 4));
             *p.err_host = 0;
-            HIP_TRY(hipHostMalloc((void**)&p.sp_counts, 8, hipHostMallocDefault));
+            SF_TRY(x.pkpool.alloc_host(&p.sp_counts, 8));
         }
     }
     // (submit_core decides asynchronously only without SystemRules; the slot it takes is e->cur)
     const bool core_async = async && !e->sys.check;
-    if (!core_async) { const int rc = drain(e); if (rc) return rc; }
+    if (!core_async) SF_TRY(drain(e));
     Slot& sl = e->slot[e->cur];
     PkStage& pk = sl.pk;
     // The slot's staging buffer: its packed inputs are free once the batch
@@ -1436,24 +1409,18 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
     // H2D of batch k back to back and overlaps the decision of k and the D2H
     // of k-1; the host blocks only to reallocate.
     const size_t N = e->cfg.max_batch;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };
-    const size_t o_ev = take(N * 8), o_xr = take(N * 8), o_xc = take(N * 8), o_ce = take(N * 4), o_og = take(N * 4);
-    const size_t o_res = take(N * 4), o_ts = take(N * 8), o_cnt = take(N * 4), o_fl = take(N), o_er = take(N * 8);
-    const size_t o_ct = take(N * 8), o_tc = take((N / 4096 + 2) * 8);
-    const size_t o_st = take(N), o_wt = take(N * 4), o_ru = take(N * 2);
-    const size_t o_wl = sp ? take(N * 8) : 0, o_rl = sp ? take(N * 8) : 0, o_sc = sp ? take(16) : 0;
-    const size_t o_ms = narrow ? take((size_t)SF_PK4_MAX_MS * 4) : 0;   // (the narrow words use o_ev's room)
-    if (pk.bytes < off) {
-        if (sl.used) HIP_TRY(hipEventSynchronize(sl.end));
-        if (pk.consumed_pending) { HIP_TRY(hipEventSynchronize(pk.consumed)); pk.consumed_pending = false; }
-        if (pk.d2h_pending) { HIP_TRY(hipEventSynchronize(pk.d2h)); pk.d2h_pending = false; }
-        if (pk.buf) hipFree(pk.buf);
-        pk.buf = nullptr; pk.bytes = 0;
-        HIP_TRY(hipMalloc((void**)&pk.buf, off));
-        pk.bytes = off;
+    Layout L;
+    const size_t o_ev = L.take(N * 8), o_xr = L.take(N * 8), o_xc = L.take(N * 8), o_ce = L.take(N * 4), o_og = L.take(N * 4);
+    const size_t o_res = L.take(N * 4), o_ts = L.take(N * 8), o_cnt = L.take(N * 4), o_fl = L.take(N), o_er = L.take(N * 8);
+    const size_t o_ct = L.take(N * 8), o_tc = L.take((N / 4096 + 2) * 8);
+    const size_t o_st = L.take(N), o_wt = L.take(N * 4), o_ru = L.take(N * 2);
+    const size_t o_wl = L.take_if(sp, N * 8), o_rl = L.take_if(sp, N * 8), o_sc = L.take_if(sp, 16);
+    const size_t o_ms = L.take_if(narrow, (size_t)SF_PK4_MAX_MS * 4);   // (the narrow words use o_ev's room)
+    if (pk.buf.bytes < L.size()) {
+        SF_TRY(pk_quiesce(sl));
+        SF_TRY(pk.buf.reserve(sl.pkpool, L.size()));
     }
-    char* B = pk.buf;
+    char* B = pk.buf.at(0);
     // The arguments, elements and contexts are sized by the batch, not by
     // max_batch, so they have a buffer of their own (pk.buf's offsets are fixed
     // and batches in flight point into it).  Two lifetimes: the staged sparse
@@ -1466,33 +1433,26 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
     // this slot waits only for `consumed`.
     const bool args = ai.n_arg_events != 0, ctx = in->context != nullptr, og_copy = host_in && in->origin;
     const uint32_t nae = ai.n_arg_events, nv = ai.n_values, ne = ai.n_elems, slots = args ? ai.arg_slots : 0;
-    size_t aoff = 0;
-    auto atake = [&](bool on, size_t bytes) { const size_t o = aoff; if (on) aoff += align_up(bytes); return o; };
     const bool st = host_in;                                   // staged inputs (device batches are read in place)
-    const size_t i_ae = atake(st && args && ai.arg_event, (size_t)nae * 4), i_ao = atake(st && args && ai.arg_off, ((size_t)nae + 1) * 4);
-    const size_t i_at = atake(st && nv, nv), i_ab = atake(st && nv, (size_t)nv * 8);
-    const size_t i_eo = atake(st && ai.elem_off, ((size_t)nv + 1) * 4), i_et = atake(st && ne, ne), i_eb = atake(st && ne, (size_t)ne * 8);
-    const size_t i_cx = atake(st && ctx, (size_t)n * 4);
-    const size_t need_in = aoff;
-    aoff = 0;
-    const size_t x_na = atake(args, n), x_at = atake(args, (size_t)n * slots), x_ab = atake(args, (size_t)n * slots * 8);
-    const size_t x_eo = atake(ai.elem_off, ((size_t)nv + 1) * 4), x_et = atake(ne, ne), x_eb = atake(ne, (size_t)ne * 8);
-    const size_t x_cx = atake(ctx, (size_t)n * 4), x_og = atake(og_copy, (size_t)n * 4);
-    const size_t need_x = aoff;
-    if (need_in > pk.a_in || need_x > pk.a_x) {
-        if (sl.used) HIP_TRY(hipEventSynchronize(sl.end));
-        if (pk.consumed_pending) { HIP_TRY(hipEventSynchronize(pk.consumed)); pk.consumed_pending = false; }
-        if (pk.d2h_pending) { HIP_TRY(hipEventSynchronize(pk.d2h)); pk.d2h_pending = false; }
-        if (pk.abuf) hipFree(pk.abuf);
-        pk.abuf = nullptr;
-        const size_t c_in = std::max(need_in, pk.a_in), c_x = std::max(need_x, pk.a_x);
+    Layout LI, LX;
+    const size_t i_ae = LI.take_if(st && args && ai.arg_event, (size_t)nae * 4), i_ao = LI.take_if(st && args && ai.arg_off, ((size_t)nae + 1) * 4);
+    const size_t i_at = LI.take_if(st && nv, nv), i_ab = LI.take_if(st && nv, (size_t)nv * 8);
+    const size_t i_eo = LI.take_if(st && ai.elem_off, ((size_t)nv + 1) * 4), i_et = LI.take_if(st && ne, ne), i_eb = LI.take_if(st && ne, (size_t)ne * 8);
+    const size_t i_cx = LI.take_if(st && ctx, (size_t)n * 4);
+    const size_t x_na = LX.take_if(args, n), x_at = LX.take_if(args, (size_t)n * slots), x_ab = LX.take_if(args, (size_t)n * slots * 8);
+    const size_t x_eo = LX.take_if(ai.elem_off, ((size_t)nv + 1) * 4), x_et = LX.take_if(ne, ne), x_eb = LX.take_if(ne, (size_t)ne * 8);
+    const size_t x_cx = LX.take_if(ctx, (size_t)n * 4), x_og = LX.take_if(og_copy, (size_t)n * 4);
+    if (LI.size() > pk.a_in || LX.size() > pk.a_x) {
+        SF_TRY(pk_quiesce(sl));
+        // (both regions grow to the largest seen: the boundary moves only here)
+        const size_t c_in = std::max(LI.size(), pk.a_in), c_x = std::max(LX.size(), pk.a_x);
         pk.a_in = pk.a_x = 0;
-        HIP_TRY(hipMalloc((void**)&pk.abuf, c_in + c_x));
+        SF_TRY(pk.abuf.reserve(sl.pkpool, c_in + c_x));
         pk.a_in = c_in; pk.a_x = c_x;
     }
-    char* AI = pk.abuf;                                        // staged inputs
+    char* AI = pk.abuf.at(0);                                  // staged inputs
     // the expanded region (no buffer: the batch needs none, and no offset is taken)
-    auto ax = [&](bool on, size_t o) -> char* { return on && pk.abuf ? pk.abuf + pk.a_in + o : nullptr; };
+    auto ax = [&](bool on, size_t o) -> char* { return on && pk.abuf.p ? pk.abuf.at(pk.a_in + o) : nullptr; };
     hipStream_t ss = e->serial ? e->stream : e->sstream;
     const uint64_t* ev = in->ev; const int64_t* xr = in->exit_ref; const int64_t* xc = in->exit_cts;
     const uint32_t* ev4 = narrow ? in->ev4 : nullptr; const uint32_t* mse = narrow ? in->ms_end : nullptr;
@@ -1596,8 +1556,7 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
     // previous batch reads)
     if (sl.used) HIP_TRY(hipStreamWaitEvent(ss, sl.end, 0));
     const PackedHook hook{expand, ai.elem_off != nullptr, nae};
-    const int rc = submit_core(e, &eb, &dv, core_async, nullptr, &hook);
-    if (rc) return rc;
+    SF_TRY(submit_core(e, &eb, &dv, core_async, nullptr, &hook));
     pk.consumed_pending = true;
     if (host_out) {
         hipStream_t d = e->serial ? e->stream : e->d2h;
@@ -1629,7 +1588,7 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
         if (!core_async) {
             HIP_TRY(hipEventSynchronize(pk.d2h));
             pk.d2h_pending = false;
-            if (sp) { const int rc = sparse_complete(pk); if (rc) return rc; }
+            if (sp) SF_TRY(sparse_complete(pk));
         }
     }
     return SF_OK;
@@ -1656,7 +1615,7 @@ static int sync_packed(sf_engine* e, const uint8_t* status) {
         pk.d2h_pending = false;
         pk.out_status = nullptr;
         e->pending &= ~(1u << k);          // checked here, not again by sf_sync
-        if (pk.sparse) { const int rc = sparse_complete(pk); if (rc) return rc; }
+        if (pk.sparse) SF_TRY(sparse_complete(pk));
         return batch_error(*pk.err_host);
     }
     return SF_OK;
@@ -1697,27 +1656,19 @@ int sf_submit_forced(sf_engine* e, const sf_event_batch* in, sf_verdicts* out, c
 static int stage_in_events(sf_engine* e, StageBuf& sb, const sf_event_batch* in, const uint8_t* status,
                            uint32_t n_status, DevBatch& b, uint8_t** dstatus, bool keep = false) {
     const uint32_t n = in->n;
-    size_t need = 0;
-    const size_t o_ts = need; need += align_up((size_t)n * 8);
-    const size_t o_cnt = need; need += align_up((size_t)n * 4);
-    const size_t o_fl = need; need += align_up((size_t)n);
-    const size_t o_er = need; need += align_up((size_t)n * 8);
-    const size_t o_ct = need; need += align_up((size_t)n * 8);
-    const size_t o_st = need; need += align_up((size_t)n + 1);
+    Layout L;
+    const size_t o_ts = L.take((size_t)n * 8), o_cnt = L.take((size_t)n * 4), o_fl = L.take(n);
+    const size_t o_er = L.take((size_t)n * 8), o_ct = L.take((size_t)n * 8), o_st = L.take((size_t)n + 1);
     const void* key[5] = {in->ts_ms, in->count, in->flags, in->entry_ref, in->create_ts};
     // the same host arrays as the round before: a cheap fingerprint of their
     // contents must match too (the contract is that the caller only appends
     // verdicts between rounds; an edited event array is restaged, not trusted)
     const int64_t fp[3] = {n ? in->ts_ms[0] : 0, n ? in->ts_ms[n - 1] : 0, n ? (int64_t)in->flags[0] : 0};
-    keep = keep && sb.p && sb.n == n && std::equal(key, key + 5, sb.key) && std::equal(fp, fp + 3, sb.fp) &&
-           need <= sb.bytes;
-    if (need > sb.bytes) {
-        if (sb.p) hipFree(sb.p);
-        sb.p = nullptr; sb.bytes = 0; sb.n = 0;
-        HIP_TRY(hipMalloc(&sb.p, need));
-        sb.bytes = need;
-    }
-    char* base = (char*)sb.p;
+    keep = keep && sb.buf.p && sb.n == n && std::equal(key, key + 5, sb.key) && std::equal(fp, fp + 3, sb.fp) &&
+           L.size() <= sb.buf.bytes;
+    if (L.size() > sb.buf.bytes) sb.n = 0;         // (nothing is staged in a new buffer)
+    SF_TRY(sb.buf.reserve(e->pool, L.size()));
+    char* base = sb.buf.at(0);
     hipStream_t s = e->stream;
     if (!keep) {
         HIP_TRY(hipMemcpyAsync(base + o_ts, in->ts_ms, (size_t)n * 8, hipMemcpyHostToDevice, s));
@@ -1771,46 +1722,40 @@ static int sx_exchange(sf_engine* e, sf_allgather_fn fn, void* ctx, const int64_
 }
 
 static int sx_recv_reserve(sf_engine* e, size_t words) {
-    if (e->sx_recv_words >= words) return SF_OK;
+    if (e->sx_recv.bytes >= words * 8) return SF_OK;
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (e->sx_recv) hipFree(e->sx_recv);
-    e->sx_recv = nullptr; e->sx_recv_words = 0;
-    HIP_TRY(hipMalloc((void**)&e->sx_recv, words * 8));
-    e->sx_recv_words = words;
-    return SF_OK;
+    return e->sx_recv.reserve(e->pool, words * 8);
 }
 
 int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, sf_verdicts* out,
                    sf_allgather_fn allgather, void* ctx) {
     if (!e || !in || !out) return fail(SF_ERR_INVALID, "null argument");
     if (in->n && (!seq || !out->status)) return fail(SF_ERR_INVALID, "missing event array");
-    { const int rc = check_event_batch(e, in); if (rc) return rc; }
+    SF_TRY(check_event_batch(e, in));
     std::lock_guard<std::mutex> lk(e->mu);
     if (!e->sys.check) return in->n ? submit_core(e, in, out, false) : SF_OK;   // nothing node-wide to decide
     if (!sx_rule_ok(e->sys))
         return fail(SF_ERR_UNSUPPORTED, "SystemRule with thread / RT / BBR checks: the event all-gather protocol "
                                         "(sf_system_plan + sf_submit_forced + sf_entry_node_add)");
     if (!allgather && !e->comm) return fail(SF_ERR_INVALID, "no exchange: sf_comm_init or an all-gather callback");
-    { const int rc = drain(e); if (rc) return rc; }
+    SF_TRY(drain(e));
     const uint32_t n = in->n, N = e->cfg.shard_count;
     hipStream_t s = e->stream;
-    if (!e->sx_msg) {
-        HIP_TRY(hipMalloc((void**)&e->sx_msg, SX_WORDS * 8));
-        HIP_TRY(hipMalloc((void**)&e->sx_ibuf, e->cfg.max_batch));
-    }
-    { const int rc = sys_buffers_ensure(e); if (rc) return rc; }
-    { const int rc = sx_recv_reserve(e, (size_t)N * SX_WORDS); if (rc) return rc; }
+    if (!e->sx_msg) SF_TRY(e->pool.alloc(&e->sx_msg, SX_WORDS * 8));
+    if (!e->sx_ibuf) SF_TRY(e->pool.alloc(&e->sx_ibuf, e->cfg.max_batch));
+    SF_TRY(sys_buffers_ensure(e));
+    SF_TRY(sx_recv_reserve(e, (size_t)N * SX_WORDS));
     const bool with_ox = in->origin || e->st.xmap;
-    { const int rc = reserve_for_batch(e, in, with_ox, in->n); if (rc) return rc; }
+    SF_TRY(reserve_for_batch(e, in, with_ox, in->n));
     Slot& sl = e->slot[e->cur];
-    { const int rc = take_slot(e, sl); if (rc) return rc; }
+    SF_TRY(take_slot(e, sl));
     Work& w = sl.w;
     DevBatch b{};
     DevVerdicts dv{};
-    { const int rc = stage_batch(e, in, out, s, b, dv); if (rc) return rc; }
+    SF_TRY(stage_batch(e, in, out, s, b, dv));
     const int64_t* dseq = seq;
     if (in->mem == SF_MEM_HOST && n) {
-        if (!e->sx_seq) HIP_TRY(hipMalloc((void**)&e->sx_seq, (size_t)e->cfg.max_batch * 8));
+        if (!e->sx_seq) SF_TRY(e->pool.alloc(&e->sx_seq, (size_t)e->cfg.max_batch * 8));
         HIP_TRY(hipMemcpyAsync(e->sx_seq, seq, (size_t)n * 8, hipMemcpyHostToDevice, s));
         dseq = e->sx_seq;
     }
@@ -1825,11 +1770,10 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
     a.g = std::__gcd((int64_t)stl.wl, (int64_t)1000);
     // every rank's message on the host: the plan step runs there (one sync per level)
     auto gather = [&](const int64_t* d_send, size_t words, std::vector<int64_t>& h) -> int {
-        const int rc = sx_exchange(e, allgather, ctx, d_send, e->sx_recv, words);
-        if (rc) return rc;
+        SF_TRY(sx_exchange(e, allgather, ctx, d_send, (int64_t*)e->sx_recv.p, words));
         if (allgather) { h.assign(e->sx_hrecv.begin(), e->sx_hrecv.begin() + words * N); return SF_OK; }
         h.resize(words * N);
-        HIP_TRY(hipMemcpyAsync(h.data(), e->sx_recv, words * N * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h.data(), e->sx_recv.p, words * N * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         return SF_OK;
     };
@@ -1839,7 +1783,7 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
     std::vector<int64_t> h;
     {
         HIP_TRY(sx_header(a, e->sx_msg, s));
-        { const int rc = gather(e->sx_msg, 5, h); if (rc) return rc; }
+        SF_TRY(gather(e->sx_msg, 5, h));
         for (uint32_t k = 0; k < N; k++) {
             const int64_t* x = &h[(size_t)k * 5];
             if (!x[4]) continue;
@@ -1853,15 +1797,15 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
     if (seq_end != INT64_MIN) {
         const uint64_t nw = (uint64_t)(C1 - C0) + 1;
         if (nw > (1u << 22)) return fail(SF_ERR_CAPACITY, "batch spans too many plan windows");
-        { const int rc = sx_recv_reserve(e, (size_t)N * nw); if (rc) return rc; }
+        SF_TRY(sx_recv_reserve(e, (size_t)N * nw));
+        DevPool tmp{HIP_MEM};
         int64_t* wbuf = nullptr;
-        HIP_TRY(hipMalloc((void**)&wbuf, nw * 8));
+        SF_TRY(tmp.alloc(&wbuf, nw * 8));
         a.c0 = C0;
         const hipError_t le = sx_winfirst(a, wbuf, (uint32_t)nw, s);
-        const int rc = le == hipSuccess ? gather(wbuf, nw, h)
-                                        : fail(SF_ERR_DEVICE, std::string("plan windows: ") + hipGetErrorString(le));
-        hipFree(wbuf);
-        if (rc) return rc;
+        if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("plan windows: ") + hipGetErrorString(le));
+        SF_TRY(gather(wbuf, nw, h));
+        tmp.release(wbuf);
         for (uint64_t k = 0; k < nw; k++) {
             int64_t m = INT64_MAX;
             for (uint32_t r = 0; r < N; r++) m = std::min(m, h[(size_t)r * nw + k]);
@@ -1874,7 +1818,7 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
     EntryNode enh;
     HIP_TRY(hipMemcpyAsync(&enh, e->en, sizeof enh, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    uint32_t* d_lq = (uint32_t*)e->sx_recv;     // (sx_locate's result: the recv buffer is free then)
+    uint32_t* d_lq = (uint32_t*)e->sx_recv.p;     // (sx_locate's result: the recv buffer is free then)
     // ---- rounds
     HIP_TRY(sx_nodelta(e->sx_msg, s));
     int64_t sp = wseq.empty() ? INT64_MAX : wseq[0];
@@ -1891,7 +1835,7 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
         for (int level = 0;; level++) {
             const hipError_t le = sx_stats(a, hp, lp, level == 0, s);
             if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("exchange stats: ") + hipGetErrorString(le));
-            { const int rc = gather(e->sx_msg, SX_WORDS, h); if (rc) return rc; }
+            SF_TRY(gather(e->sx_msg, SX_WORDS, h));
             levels++;
             if (level == 0) {
                 // the node's ENTRY_NODE contribution of the last sub-batch (its plan window is the key)
@@ -1923,7 +1867,7 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
             if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("exchange mask: ") + hipGetErrorString(le));
             DevBatch v;
             DevVerdicts dvv;
-            { const int rc = decide_view(e, sl, stl, b, dv, lp, lq, with_ox, v, dvv); if (rc) return rc; }
+            SF_TRY(decide_view(e, sl, stl, b, dv, lp, lq, with_ox, v, dvv));
             le = launch_entry_delta(stl, v, dvv.status, e->en_acc, e->sx_msg, wkey[j], s);
             if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("exchange delta: ") + hipGetErrorString(le));
         } else {
@@ -1950,19 +1894,19 @@ int sf_system_plan(sf_engine* e, const sf_event_batch* in, const uint8_t* status
     if (in->n > e->cfg.max_batch) return fail(SF_ERR_CAPACITY, "batch larger than max_batch");
     if (p >= in->n) return fail(SF_ERR_INVALID, "plan position past the batch");
     std::lock_guard<std::mutex> lk(e->mu);
-    { const int rc = drain(e); if (rc) return rc; }
+    SF_TRY(drain(e));
     const uint32_t n = in->n;
     if (!e->sys.check) {                                   // no SystemRule: nothing is forced
         std::memset(sys_mask + p, SYS_NONE, n - p);
         *q = n;
         return SF_OK;
     }
-    { const int rc = sys_buffers_ensure(e); if (rc) return rc; }
+    SF_TRY(sys_buffers_ensure(e));
     DevBatch b;
     uint8_t* dstatus = nullptr;
     // a later round of the same merged stream (p > 0, same arrays): the events
     // staged for the round before are reused, only the verdicts are copied
-    { const int rc = stage_in_events(e, e->plan_sb, in, status, p, b, &dstatus, p > 0); if (rc) return rc; }
+    SF_TRY(stage_in_events(e, e->plan_sb, in, status, p, b, &dstatus, p > 0));
     hipStream_t s = e->stream;
     DevState stl = e->st;
     hipError_t le = sys_plan(stl, b, dstatus, e->sys_mask, e->sys, e->en, p, e->sys_plan, e->sys_pa, e->sys_pb, s);
@@ -1982,14 +1926,28 @@ int sf_entry_node_add(sf_engine* e, const sf_event_batch* in, const uint8_t* sta
         return fail(SF_ERR_INVALID, "sf_entry_node_add takes host arrays");
     if (in->n > e->cfg.max_batch) return fail(SF_ERR_CAPACITY, "batch larger than max_batch");
     std::lock_guard<std::mutex> lk(e->mu);
-    { const int rc = drain(e); if (rc) return rc; }
+    SF_TRY(drain(e));
     if (!in->n) return SF_OK;
     DevBatch b;
     uint8_t* dstatus = nullptr;
-    { const int rc = stage_in_events(e, e->en_sb, in, status, in->n, b, &dstatus); if (rc) return rc; }
+    SF_TRY(stage_in_events(e, e->en_sb, in, status, in->n, b, &dstatus));
     hipError_t le = launch_entry_node(e->st, b, dstatus, e->en, e->en_acc, e->stream);
     if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("entry node: ") + hipGetErrorString(le));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return SF_OK;
+}
+
+// A kernel's small result: `bytes` of scratch, launch(scratch) on `stream`, the
+// copy back and one sync; the scratch is freed on every path.
+static int read_back(sf_engine* e, void* host, size_t bytes, const char* what,
+                     const std::function<hipError_t(void*)>& launch) {
+    DevPool tmp{HIP_MEM};
+    void* d = nullptr;
+    SF_TRY(tmp.alloc(&d, bytes));
+    hipError_t he = launch(d);
+    if (he == hipSuccess) he = hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    if (he != hipSuccess) return fail(SF_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(he));
     return SF_OK;
 }
 
@@ -2047,16 +2005,12 @@ static int read_aux(sf_engine* e, uint32_t resource, uint32_t kind, uint32_t id,
     uint32_t l;
     if (!local_of(e, resource, &l)) return fail(SF_ERR_INVALID, "resource outside this shard");
     std::lock_guard<std::mutex> lk(e->mu);
-    { const int rc = drain(e); if (rc) return rc; }
+    SF_TRY(drain(e));
     if (!e->st.xtab) return fail(SF_ERR_INVALID, "no origin / context node is kept");
-    uint32_t* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, 4));
     uint32_t k = XNONE;
-    hipError_t le = launch_aux_find(e->st, pkey_hi(l, PK_AUX, kind, 0), id, d, e->stream);
-    if (le == hipSuccess) le = hipMemcpyAsync(&k, d, 4, hipMemcpyDeviceToHost, e->stream);
-    if (le == hipSuccess) le = hipStreamSynchronize(e->stream);
-    hipFree(d);
-    if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("aux find: ") + hipGetErrorString(le));
+    SF_TRY(read_back(e, &k, 4, "aux find", [&](void* d) {
+        return launch_aux_find(e->st, pkey_hi(l, PK_AUX, kind, 0), id, (uint32_t*)d, e->stream);
+    }));
     if (k == XNONE || k >= e->st.ax_cap) return fail(SF_ERR_INVALID, "that origin / context node is not kept");
     DevState hs = e->st;
     hs.ax_chunks = e->ax_host.data();            // host mirror of the chunk directory
@@ -2073,7 +2027,7 @@ int sf_read_context_node(sf_engine* e, uint32_t context, uint32_t resource, sf_n
 int sf_read_entry_node(sf_engine* e, sf_node_state* out) {
     if (!e || !out) return fail(SF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(e->mu);
-    { const int rc = en_fence(e); if (rc) return rc; }
+    SF_TRY(en_fence(e));
     EntryNode en;
     HIP_TRY(hipMemcpyAsync(&en, e->en, sizeof en, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -2099,23 +2053,18 @@ int sf_node_digests(sf_engine* e, uint64_t* out, uint32_t n_rows) {
     if (!e || (n_rows && !out)) return fail(SF_ERR_INVALID, "null argument");
     if (n_rows > e->R) return fail(SF_ERR_INVALID, "n_rows above max_resources");
     std::lock_guard<std::mutex> lk(e->mu);
-    { const int rc = drain(e); if (rc) return rc; }
+    SF_TRY(drain(e));
     if (!n_rows) return SF_OK;
-    unsigned long long* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, (size_t)n_rows * 8));
-    hipError_t he = launch_node_digests(e->st, n_rows, d, e->stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(out, d, (size_t)n_rows * 8, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    hipFree(d);
-    if (he != hipSuccess) return fail(SF_ERR_DEVICE, std::string("node digests: ") + hipGetErrorString(he));
-    return SF_OK;
+    return read_back(e, out, (size_t)n_rows * 8, "node digests", [&](void* d) {
+        return launch_node_digests(e->st, n_rows, (unsigned long long*)d, e->stream);
+    });
 }
 
 int sf_read_rule_states(sf_engine* e, uint32_t first, uint32_t n, sf_rule_state* out) {
     if (!e || (n && !out)) return fail(SF_ERR_INVALID, "null argument");
     if ((uint64_t)first + n > e->n_flow) return fail(SF_ERR_INVALID, "rule index");
     std::lock_guard<std::mutex> lk(e->mu);
-    { const int rc = drain(e); if (rc) return rc; }
+    SF_TRY(drain(e));
     if (!n) return SF_OK;
     std::vector<DevRuleState> all(e->n_flow);      // CSR order: the positions of a range are not contiguous
     HIP_TRY(hipMemcpyAsync(all.data(), e->st.rstate, all.size() * sizeof(DevRuleState), hipMemcpyDeviceToHost,
@@ -2132,29 +2081,29 @@ int sf_read_rule_states(sf_engine* e, uint32_t first, uint32_t n, sf_rule_state*
 int sf_snapshot(sf_engine* e, int64_t now_ms, sf_metric_row* out, uint32_t cap, uint32_t* n_out) {
     if (!e || !n_out || (cap && !out)) return fail(SF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(e->mu);
-    { const int rc = en_fence(e); if (rc) return rc; }
+    SF_TRY(en_fence(e));
     *n_out = 0;
     hipStream_t s = e->stream;
-    if (!e->snap_counts) {
-        HIP_TRY(hipMalloc((void**)&e->snap_counts, (size_t)e->R * 4));
-        HIP_TRY(hipMalloc((void**)&e->snap_offsets, (size_t)e->R * 4));
-        HIP_TRY(hipMalloc((void**)&e->snap_total, 4));
-        HIP_TRY(rocprim_scan_bytes(e->R, &e->snap_scan_bytes));
-        HIP_TRY(hipMalloc(&e->snap_scan, std::max<size_t>(e->snap_scan_bytes, 16)));
+    if (!e->snap_ready) {
+        const int rc = [&]() -> int {
+            SF_TRY(e->pool.alloc(&e->snap_counts, (size_t)e->R * 4));
+            SF_TRY(e->pool.alloc(&e->snap_offsets, (size_t)e->R * 4));
+            SF_TRY(e->pool.alloc(&e->snap_total, 4));
+            HIP_TRY(rocprim_scan_bytes(e->R, &e->snap_scan_bytes));
+            return e->pool.alloc(&e->snap_scan, min16(e->snap_scan_bytes));
+        }();
+        if (rc) { e->pool.release_all(e->snap_counts, e->snap_offsets, e->snap_total, e->snap_scan); return rc; }
+        e->snap_ready = true;
     }
-    if (cap > e->snap_cap) {
-        if (e->snap_rows) hipFree(e->snap_rows);
-        e->snap_rows = nullptr;
-        HIP_TRY(hipMalloc((void**)&e->snap_rows, (size_t)cap * sizeof(sf_metric_row)));
-        e->snap_cap = cap;
-    }
+    SF_TRY(e->snap_rows.reserve(e->pool, (size_t)cap * sizeof(sf_metric_row)));
+    sf_metric_row* rows = (sf_metric_row*)e->snap_rows.p;
     HIP_TRY(launch_snapshot(e->st, now_ms, e->cfg.shard_count, e->cfg.shard_index, e->snap_counts, e->snap_offsets,
-                            e->snap_rows, cap, e->snap_total, e->snap_scan, e->snap_scan_bytes, s));
+                            rows, cap, e->snap_total, e->snap_scan, e->snap_scan_bytes, s));
     uint32_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, e->snap_total, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const uint32_t k = std::min(total, cap);
-    if (k) HIP_TRY(hipMemcpy(out, e->snap_rows, (size_t)k * sizeof(sf_metric_row), hipMemcpyDeviceToHost));
+    if (k) HIP_TRY(hipMemcpy(out, rows, (size_t)k * sizeof(sf_metric_row), hipMemcpyDeviceToHost));
     *n_out = total;
     return total <= cap ? SF_OK : fail(SF_ERR_CAPACITY, "snapshot rows exceed cap");
 }
@@ -2165,80 +2114,77 @@ int sf_load_resource_names(sf_engine* e, const char* bytes, const uint64_t* offs
     for (uint32_t i = 0; i < n; i++)
         if (offsets[i + 1] < offsets[i]) return fail(SF_ERR_INVALID, "name offsets must be non-decreasing");
     std::lock_guard<std::mutex> lk(e->mu);
-    void* old[] = {e->nm_bytes, e->nm_off, e->nm_types};
     HIP_TRY(hipStreamSynchronize(e->stream));
-    for (void* p : old) if (p) hipFree(p);
-    e->nm_bytes = nullptr; e->nm_off = nullptr; e->nm_types = nullptr; e->n_names = 0;
+    e->pool.release_all(e->nm_bytes, e->nm_off, e->nm_types);
+    e->n_names = 0;
     const uint64_t nb = n ? offsets[n] - offsets[0] : 0;
-    HIP_TRY(hipMalloc((void**)&e->nm_bytes, std::max<uint64_t>(nb, 16)));
-    HIP_TRY(hipMalloc((void**)&e->nm_off, ((size_t)n + 1) * 8));
+    SF_TRY(e->pool.alloc(&e->nm_bytes, min16(nb)));
+    SF_TRY(e->pool.alloc(&e->nm_off, ((size_t)n + 1) * 8));
     if (nb) HIP_TRY(hipMemcpy(e->nm_bytes, bytes + offsets[0], nb, hipMemcpyHostToDevice));
     std::vector<uint64_t> off(offsets, offsets + n + 1);
     for (auto& o : off) o -= offsets[0];
     HIP_TRY(hipMemcpy(e->nm_off, off.data(), off.size() * 8, hipMemcpyHostToDevice));
     if (types) {
-        HIP_TRY(hipMalloc((void**)&e->nm_types, std::max<size_t>((size_t)n * 4, 16)));
+        SF_TRY(e->pool.alloc(&e->nm_types, min16((size_t)n * 4)));
         if (n) HIP_TRY(hipMemcpy(e->nm_types, types, (size_t)n * 4, hipMemcpyHostToDevice));
     }
     e->n_names = n;
     return SF_OK;
 }
 
-static int ml_reserve(sf_engine* e, uint32_t rows) {
+// The metric log's buffers: the per-node ones and the events on first use,
+// the per-row ones for `rows` rows, the scan / sort scratch for both.  A
+// failure anywhere leaves none (ml_pool cleared), and the next call starts over.
+static int ml_build(sf_engine* e, uint32_t rows) {
+    auto& ml = e->ml;
+    DevPool& m = e->ml_pool;
     const uint32_t nodes = e->R + 1;
-    if (!e->ml_mask) {
-        HIP_TRY(hipMalloc((void**)&e->ml_mask, (size_t)nodes * 8));
-        HIP_TRY(hipMalloc((void**)&e->ml_counts, (size_t)nodes * 4));
-        HIP_TRY(hipMalloc((void**)&e->ml_offsets, (size_t)nodes * 4));
-        HIP_TRY(hipMalloc((void**)&e->ml_total, 4));
-        HIP_TRY(hipMalloc((void**)&e->ml_bytes, 8));
-        for (auto& x : e->ml_ev) HIP_TRY(hipEventCreate(&x));
+    if (!ml.ready) {
+        SF_TRY(m.alloc(&ml.mask, (size_t)nodes * 8));
+        SF_TRY(m.alloc(&ml.counts, (size_t)nodes * 4));
+        SF_TRY(m.alloc(&ml.offsets, (size_t)nodes * 4));
+        SF_TRY(m.alloc(&ml.total, 4));
+        SF_TRY(m.alloc(&ml.bytes, 8));
+        for (auto& x : e->ml_ev) if (!x) HIP_TRY(hipEventCreate(&x));
+        ml.ready = true;
     }
-    if (rows > e->ml_row_cap || !e->ml_rows) {
+    if (rows > ml.row_cap || !ml.row_cap) {
         const uint32_t cap = std::max<uint32_t>(rows, 1024);
-        void* old[] = {e->ml_rows, e->ml_keys, e->ml_order, e->ml_len, e->ml_off};
-        for (void* p : old) if (p) hipFree(p);
-        e->ml_rows = nullptr; e->ml_keys = nullptr; e->ml_order = nullptr; e->ml_len = nullptr; e->ml_off = nullptr;
-        e->ml_row_cap = 0;
-        HIP_TRY(hipMalloc((void**)&e->ml_rows, (size_t)cap * sizeof(sf_metric_row)));
-        HIP_TRY(hipMalloc((void**)&e->ml_keys, (size_t)cap * 2));
-        HIP_TRY(hipMalloc((void**)&e->ml_order, (size_t)cap * 8));
-        HIP_TRY(hipMalloc((void**)&e->ml_len, (size_t)cap * 8));
-        HIP_TRY(hipMalloc((void**)&e->ml_off, (size_t)cap * 8));
-        e->ml_row_cap = cap;
+        m.release_all(ml.rows, ml.keys, ml.order, ml.len, ml.off);
+        ml.row_cap = 0;
+        SF_TRY(m.alloc(&ml.rows, (size_t)cap * sizeof(sf_metric_row)));
+        SF_TRY(m.alloc(&ml.keys, (size_t)cap * 2));
+        SF_TRY(m.alloc(&ml.order, (size_t)cap * 8));
+        SF_TRY(m.alloc(&ml.len, (size_t)cap * 8));
+        SF_TRY(m.alloc(&ml.off, (size_t)cap * 8));
+        ml.row_cap = cap;
     }
     size_t tb = 0;
-    HIP_TRY(mlog_temp_bytes(nodes, e->ml_row_cap, &tb));
-    if (tb > e->ml_tmp_bytes) {
-        if (e->ml_tmp) hipFree(e->ml_tmp);
-        e->ml_tmp = nullptr; e->ml_tmp_bytes = 0;
-        HIP_TRY(hipMalloc(&e->ml_tmp, tb));
-        e->ml_tmp_bytes = tb;
-    }
-    return SF_OK;
+    HIP_TRY(mlog_temp_bytes(nodes, ml.row_cap, &tb));
+    return ml.tmp.reserve(m, tb);
+}
+static int ml_reserve(sf_engine* e, uint32_t rows) {
+    const int rc = ml_build(e, rows);
+    if (rc) { e->ml_pool.clear(); e->ml = {}; }
+    return rc;
 }
 
 // line lengths -> offsets -> lines, copied to the caller's host buffer
 static int ml_format(sf_engine* e, const uint32_t* order, uint32_t n, int64_t tz, char* out, uint64_t cap,
                      uint64_t* len_out) {
     hipStream_t s = e->stream;
-    HIP_TRY(launch_fmt_len(e->ml_rows, order, n, e->nm_bytes, e->nm_off, e->nm_types, e->n_names, tz, e->ml_len,
-                           e->ml_off, e->ml_bytes, e->ml_tmp, e->ml_tmp_bytes, s));
+    HIP_TRY(launch_fmt_len(e->ml.rows, order, n, e->nm_bytes, e->nm_off, e->nm_types, e->n_names, tz, e->ml.len,
+                           e->ml.off, e->ml.bytes, e->ml.tmp.p, e->ml.tmp.bytes, s));
     uint64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, e->ml_bytes, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&total, e->ml.bytes, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     *len_out = total;
     if (total > cap) return fail(SF_ERR_CAPACITY, "metric log bytes exceed cap");
-    if (total > e->ml_out_cap) {
-        if (e->ml_out) hipFree(e->ml_out);
-        e->ml_out = nullptr; e->ml_out_cap = 0;
-        HIP_TRY(hipMalloc((void**)&e->ml_out, total));
-        e->ml_out_cap = total;
-    }
-    HIP_TRY(launch_fmt_write(e->ml_rows, order, n, e->nm_bytes, e->nm_off, e->nm_types, e->n_names, tz, e->ml_off,
-                             e->ml_out, s));
+    SF_TRY(e->ml.out.reserve(e->ml_pool, total));
+    HIP_TRY(launch_fmt_write(e->ml.rows, order, n, e->nm_bytes, e->nm_off, e->nm_types, e->n_names, tz, e->ml.off,
+                             (char*)e->ml.out.p, s));
     HIP_TRY(hipEventRecord(e->ml_ev[2], s));
-    if (total) HIP_TRY(hipMemcpyAsync(out, e->ml_out, total, hipMemcpyDeviceToHost, s));
+    if (total) HIP_TRY(hipMemcpyAsync(out, e->ml.out.p, total, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return SF_OK;
 }
@@ -2247,11 +2193,10 @@ int sf_metric_log(sf_engine* e, int64_t now_ms, int64_t tz_offset_ms, int includ
                   uint64_t cap, uint64_t* len_out, uint32_t* n_lines) {
     if (!e || !len_out || (cap && !out)) return fail(SF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(e->mu);
-    { const int rc = en_fence(e); if (rc) return rc; }
+    SF_TRY(en_fence(e));
     *len_out = 0;
     if (n_lines) *n_lines = 0;
-    int rc = ml_reserve(e, 0);
-    if (rc) return rc;
+    SF_TRY(ml_reserve(e, 0));
     hipStream_t s = e->stream;
     const bool with_en = include_entry_node != 0;
     const uint32_t nodes = e->R + (with_en ? 1u : 0u);
@@ -2259,7 +2204,7 @@ int sf_metric_log(sf_engine* e, int64_t now_ms, int64_t tz_offset_ms, int includ
     // (its windows; lastFetchTime stays this engine's, MetricTimerListener.java:40-69)
     EntryNode* en = e->en;
     if (with_en && e->report_set) {
-        if (!e->en_report) HIP_TRY(hipMalloc((void**)&e->en_report, sizeof(EntryNode)));
+        if (!e->en_report) SF_TRY(e->pool.alloc(&e->en_report, sizeof(EntryNode)));
         HIP_TRY(hipMemcpyAsync(e->en_report, &e->report, sizeof(EntryNode), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(&e->en_report->last_fetch, &e->en->last_fetch, 8, hipMemcpyDeviceToDevice, s));
         en = e->en_report;
@@ -2268,21 +2213,19 @@ int sf_metric_log(sf_engine* e, int64_t now_ms, int64_t tz_offset_ms, int includ
     if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)nodes + 3) / 4, (uint64_t)cus * 16);
     HIP_TRY(hipEventRecord(e->ml_ev[0], s));
-    HIP_TRY(launch_mlog_count(e->st, en, with_en, e->cfg.shard_count, e->cfg.shard_index, now_ms, e->ml_mask,
-                              e->ml_counts, e->ml_offsets, e->ml_total, e->ml_tmp, e->ml_tmp_bytes, grid, e->ml_ev[1], s));
+    HIP_TRY(launch_mlog_count(e->st, en, with_en, e->cfg.shard_count, e->cfg.shard_index, now_ms, e->ml.mask,
+                              e->ml.counts, e->ml.offsets, e->ml.total, e->ml.tmp.p, e->ml.tmp.bytes, grid, e->ml_ev[1], s));
     uint32_t rows = 0;
-    HIP_TRY(hipMemcpyAsync(&rows, e->ml_total, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&rows, e->ml.total, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    rc = ml_reserve(e, rows);
-    if (rc) return rc;
-    uint32_t* ord = e->ml_order;
-    HIP_TRY(launch_mlog_rows(e->st, en, with_en, e->cfg.shard_count, e->cfg.shard_index, now_ms, e->ml_mask,
-                             e->ml_offsets, rows, e->ml_rows, e->ml_keys, e->ml_keys + e->ml_row_cap, ord,
-                             ord + e->ml_row_cap, e->ml_tmp, e->ml_tmp_bytes, grid, s));
+    SF_TRY(ml_reserve(e, rows));
+    uint32_t* ord = e->ml.order;
+    HIP_TRY(launch_mlog_rows(e->st, en, with_en, e->cfg.shard_count, e->cfg.shard_index, now_ms, e->ml.mask,
+                             e->ml.offsets, rows, e->ml.rows, e->ml.keys, e->ml.keys + e->ml.row_cap, ord,
+                             ord + e->ml.row_cap, e->ml.tmp.p, e->ml.tmp.bytes, grid, s));
     if (n_lines) *n_lines = rows;
     if (en != e->en) HIP_TRY(hipMemcpyAsync(&e->en->last_fetch, &en->last_fetch, 8, hipMemcpyDeviceToDevice, s));
-    rc = ml_format(e, ord + e->ml_row_cap, rows, tz_offset_ms, out, cap, len_out);
-    if (rc) return rc;
+    SF_TRY(ml_format(e, ord + e->ml.row_cap, rows, tz_offset_ms, out, cap, len_out));
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, e->ml_ev[0], e->ml_ev[1]) == hipSuccess) e->stats.metric_scan_ms = ms;
     if (hipEventElapsedTime(&ms, e->ml_ev[0], e->ml_ev[2]) == hipSuccess) e->stats.metric_log_ms = ms;
@@ -2294,9 +2237,8 @@ int sf_format_metric_rows(sf_engine* e, const sf_metric_row* rows, uint32_t n, i
     if (!e || !len_out || (n && !rows) || (cap && !out)) return fail(SF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(e->mu);
     *len_out = 0;
-    int rc = ml_reserve(e, n);
-    if (rc) return rc;
-    if (n) HIP_TRY(hipMemcpyAsync(e->ml_rows, rows, (size_t)n * sizeof(sf_metric_row), hipMemcpyHostToDevice,
+    SF_TRY(ml_reserve(e, n));
+    if (n) HIP_TRY(hipMemcpyAsync(e->ml.rows, rows, (size_t)n * sizeof(sf_metric_row), hipMemcpyHostToDevice,
                                   e->stream));
     return ml_format(e, nullptr, n, tz_offset_ms, out, cap, len_out);
 }
@@ -2370,28 +2312,27 @@ static int tok_rebuild(sf_engine* e, bool reset_state) {
     }
     hipStream_t s = e->stream;
     auto upload = [&](void** dst, const void* src, size_t bytes) -> int {
-        if (*dst) { hipFree(*dst); *dst = nullptr; }
-        HIP_TRY(hipMalloc(dst, std::max<size_t>(bytes, 16)));
+        e->pool.release(*dst);
+        SF_TRY(e->pool.alloc(dst, min16(bytes)));
         if (bytes) HIP_TRY(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, s));
         return SF_OK;
     };
-    int rc;
-    if ((rc = upload((void**)&ts.rules, rules.data(), rules.size() * sizeof(ClRule)))) return rc;
-    if ((rc = upload((void**)&ts.idtab, tab.data(), tab.size() * sizeof(IdSlot)))) return rc;
-    if ((rc = upload((void**)&ts.ns, ns.data(), ns.size() * sizeof(ClNs)))) return rc;
-    if ((rc = upload((void**)&ts.items, items.data(), items.size() * sizeof(DevHotItem)))) return rc;
-    if (ts.rmulti) { hipFree(ts.rmulti); ts.rmulti = nullptr; }
-    HIP_TRY(hipMalloc((void**)&ts.rmulti, std::max<size_t>(rules.size(), 16)));   // per-call multi-value flags
+    SF_TRY(upload((void**)&ts.rules, rules.data(), rules.size() * sizeof(ClRule)));
+    SF_TRY(upload((void**)&ts.idtab, tab.data(), tab.size() * sizeof(IdSlot)));
+    SF_TRY(upload((void**)&ts.ns, ns.data(), ns.size() * sizeof(ClNs)));
+    SF_TRY(upload((void**)&ts.items, items.data(), items.size() * sizeof(DevHotItem)));
+    e->pool.release(ts.rmulti);
+    SF_TRY(e->pool.alloc(&ts.rmulti, min16(rules.size())));   // per-call multi-value flags
     ts.id_mask = cap - 1;
     ts.n_flow = nf; ts.n_rules = nf + np; ts.n_ns = (uint32_t)ns.size();
     if (reset_state) {
-        if (ts.fstate) { hipFree(ts.fstate); ts.fstate = nullptr; }
-        HIP_TRY(hipMalloc((void**)&ts.fstate, std::max<size_t>(nf, 1) * sizeof(ClFlowState)));
+        e->pool.release(ts.fstate);
+        SF_TRY(e->pool.alloc(&ts.fstate, std::max<size_t>(nf, 1) * sizeof(ClFlowState)));
         HIP_TRY(tok_init_flow_state(ts.fstate, nf, s));
         if (!ts.cptab) {
             uint64_t pc = 1024;
             while (pc < std::max<uint64_t>(e->cfg.param_capacity, 1024)) pc <<= 1;
-            HIP_TRY(hipMalloc((void**)&ts.cptab, pc * sizeof(CpSlot)));
+            SF_TRY(e->pool.alloc(&ts.cptab, pc * sizeof(CpSlot)));
             ts.cp_mask = pc - 1;
         }
         HIP_TRY(hipMemsetAsync(ts.cptab, 0, (ts.cp_mask + 1) * sizeof(CpSlot), s));
@@ -2413,17 +2354,17 @@ static int cc_tables(sf_engine* e, const std::vector<int32_t>* now) {
         if (it != by_id.end()) cfg[i] = CcCfg{it->second->resource_timeout_ms, it->second->client_offline_time_ms};
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (cs.cfg) { hipFree((void*)cs.cfg); cs.cfg = nullptr; }
-    HIP_TRY(hipMalloc((void**)&cs.cfg, m * sizeof(CcCfg)));
+    e->pool.release(cs.cfg);
+    SF_TRY(e->pool.alloc(&cs.cfg, m * sizeof(CcCfg)));
     HIP_TRY(hipMemcpy((void*)cs.cfg, cfg.data(), m * sizeof(CcCfg), hipMemcpyHostToDevice));
     if (now || !cs.now) {
-        if (cs.now) { hipFree(cs.now); cs.now = nullptr; }
-        HIP_TRY(hipMalloc((void**)&cs.now, m * 4));
+        e->pool.release(cs.now);
+        SF_TRY(e->pool.alloc(&cs.now, m * 4));
         if (now) HIP_TRY(hipMemcpy(cs.now, now->data(), m * 4, hipMemcpyHostToDevice));
         else HIP_TRY(hipMemset(cs.now, 0, m * 4));
     }
     if (!cs.ctr) {
-        HIP_TRY(hipMalloc((void**)&cs.ctr, sizeof(CcCounters)));
+        SF_TRY(e->pool.alloc(&cs.ctr, sizeof(CcCounters)));
         HIP_TRY(hipMemset(cs.ctr, 0, sizeof(CcCounters)));
     }
     return SF_OK;
@@ -2438,8 +2379,8 @@ int sf_load_namespaces(sf_engine* e, const sf_namespace* ns, uint32_t n) {
     LimState z;
     for (int k = 0; k < LIM_S; k++) { z.ws[k] = WS_NONE; z.v[k] = 0; }
     std::vector<LimState> lim(std::max<uint32_t>(n, 1), z);
-    if (e->ts.lim) { hipFree(e->ts.lim); e->ts.lim = nullptr; }
-    HIP_TRY(hipMalloc((void**)&e->ts.lim, lim.size() * sizeof(LimState)));
+    e->pool.release(e->ts.lim);
+    SF_TRY(e->pool.alloc(&e->ts.lim, lim.size() * sizeof(LimState)));
     HIP_TRY(hipMemcpyAsync(e->ts.lim, lim.data(), lim.size() * sizeof(LimState), hipMemcpyHostToDevice, e->stream));
     return tok_rebuild(e, false);
 }
@@ -2482,33 +2423,17 @@ int sf_load_cluster_rules(sf_engine* e, const sf_cluster_flow_rule* flow, uint32
     return cc_tables(e, &now);
 }
 
-static int tok_work_ensure(sf_engine* e, uint32_t n) {
-    if (n <= e->tw_cap) return SF_OK;
-    free_tok_work(e->tw);
-    TokWork& w = e->tw;
-    const size_t N = std::max<uint32_t>(n, e->cfg.max_batch);
-    auto A = [&](void** p, size_t bytes) -> int { HIP_TRY(hipMalloc(p, std::max<size_t>(bytes, 16))); return SF_OK; };
-    int rc = 0;
-    rc |= A((void**)&w.nskey_in, N); rc |= A((void**)&w.nskey_out, N);
-    rc |= A((void**)&w.idx_in, N * 4); rc |= A((void**)&w.idx_out, N * 4);
-    rc |= A((void**)&w.key_in, N * 8); rc |= A((void**)&w.key_out, N * 8);
-    rc |= A((void**)&w.rule_of, N * 4); rc |= A((void**)&w.pending, N);
-    rc |= A((void**)&w.head, std::max<size_t>(N, 512) * 4); rc |= A((void**)&w.head_scan, N * 4);
-    rc |= A((void**)&w.seg_start, (N + 1) * 4); rc |= A((void**)&w.n_seg, 4);
-    if (rc) return SF_ERR_NOMEM;
-    HIP_TRY(tok_query_temp((uint32_t)N, &w.sort8_bytes, &w.sort64_bytes, &w.scan_bytes));
-    rc |= A(&w.sort8_tmp, w.sort8_bytes); rc |= A(&w.sort64_tmp, w.sort64_bytes); rc |= A(&w.scan_tmp, w.scan_bytes);
-    if (rc) return SF_ERR_NOMEM;
-    e->tw_cap = (uint32_t)N;
-    return SF_OK;
-}
+// the scratch sizes of the work sets (sf_worksets.h) as rocPRIM states them
+static int tok_temp_query(uint32_t n, size_t* s8, size_t* s64, size_t* scan) { HIP_TRY(tok_query_temp(n, s8, s64, scan)); return SF_OK; }
+static int cc_temp_query(uint32_t n, size_t* bytes) { HIP_TRY(cc_query_temp(n, bytes)); return SF_OK; }
+static int dg_temp_query(uint32_t n, uint32_t key_bits, size_t* bytes) { HIP_TRY(dg_sort_bytes(n, key_bits, bytes)); return SF_OK; }
 
 // token state present (rules built, namespace limiter allocated); caller holds e->mu
 static int tok_ready(sf_engine* e) {
-    if (!e->ts.rules) { int r2 = tok_rebuild(e, true); if (r2) return r2; }
+    if (!e->ts.rules) SF_TRY(tok_rebuild(e, true));
     if (!e->ts.lim) {
         LimState z; for (int k = 0; k < LIM_S; k++) { z.ws[k] = WS_NONE; z.v[k] = 0; }
-        HIP_TRY(hipMalloc((void**)&e->ts.lim, sizeof(LimState)));
+        SF_TRY(e->pool.alloc(&e->ts.lim, sizeof(LimState)));
         HIP_TRY(hipMemcpy(e->ts.lim, &z, sizeof z, hipMemcpyHostToDevice));
     }
     return SF_OK;
@@ -2521,9 +2446,8 @@ int sf_request_tokens(sf_engine* e, const sf_token_batch* in, sf_token_results* 
     if ((in->param_tag == nullptr) != (in->param_bits == nullptr)) return fail(SF_ERR_INVALID, "param_tag/param_bits");
     std::lock_guard<std::mutex> lk(e->mu);
     const uint32_t n = in->n;
-    int rc = tok_work_ensure(e, n);
-    if (rc) return fail(rc, "token work buffers");
-    { int r2 = tok_ready(e); if (r2) return r2; }
+    SF_TRY(tok_work_ensure(e->tw, n, e->cfg.max_batch, tok_temp_query));
+    SF_TRY(tok_ready(e));
     hipStream_t s = e->stream;
     TokBatch b{};
     b.n = n;
@@ -2535,19 +2459,13 @@ int sf_request_tokens(sf_engine* e, const sf_token_batch* in, sf_token_results* 
         else HIP_TRY(hipMemcpy(&n_vals, in->param_off + n, 4, hipMemcpyDeviceToHost));
     }
     // staging: inputs then outputs, 256-B aligned
-    size_t off_fid = 0, off_cnt = align_up(off_fid + (size_t)n * 8), off_fl = align_up(off_cnt + (size_t)n * 4),
-           off_ts = align_up(off_fl + n), off_tag = align_up(off_ts + (size_t)n * 8),
-           off_bits = align_up(off_tag + (has_param ? n_vals : 0)),
-           off_po = align_up(off_bits + (has_param ? (size_t)n_vals * 8 : 0)),
-           off_st = align_up(off_po + (in->param_off ? ((size_t)n + 1) * 4 : 0)),
-           off_rem = align_up(off_st + n), off_wt = align_up(off_rem + (size_t)n * 4), need = align_up(off_wt + (size_t)n * 4);
-    if (need > e->tok_stage_bytes) {
-        if (e->tok_stage) hipFree(e->tok_stage);
-        e->tok_stage = nullptr;
-        HIP_TRY(hipMalloc(&e->tok_stage, need));
-        e->tok_stage_bytes = need;
-    }
-    char* base = (char*)e->tok_stage;
+    Layout L;
+    const size_t off_fid = L.take((size_t)n * 8), off_cnt = L.take((size_t)n * 4), off_fl = L.take(n), off_ts = L.take((size_t)n * 8);
+    const size_t off_tag = L.take_if(has_param, n_vals), off_bits = L.take_if(has_param, (size_t)n_vals * 8);
+    const size_t off_po = L.take_if(in->param_off, ((size_t)n + 1) * 4);
+    const size_t off_st = L.take(n), off_rem = L.take((size_t)n * 4), off_wt = L.take((size_t)n * 4);
+    SF_TRY(e->tok_stage.reserve(e->pool, L.size()));
+    char* base = e->tok_stage.at(0);
     if (in->mem == SF_MEM_HOST) {
         HIP_TRY(hipMemcpyAsync(base + off_fid, in->flow_id, (size_t)n * 8, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(base + off_cnt, in->count, (size_t)n * 4, hipMemcpyHostToDevice, s));
@@ -2577,7 +2495,7 @@ int sf_request_tokens(sf_engine* e, const sf_token_batch* in, sf_token_results* 
         o.status = out->status; o.remaining = out->remaining; o.wait = out->wait_ms;
     }
     HIP_TRY(hipMemsetAsync(e->st.err, 0, sizeof(int32_t), s));
-    hipError_t le = tok_launch(e->ts, e->tw, b, o, s);
+    hipError_t le = tok_launch(e->ts, e->tw.w, b, o, s);
     if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("token launch: ") + hipGetErrorString(le));
     if (host_out) {
         HIP_TRY(hipMemcpyAsync(out->status, o.status, n, hipMemcpyDeviceToHost, s));
@@ -2642,7 +2560,7 @@ int sf_serve_frames(sf_engine* e, const sf_wire_batch* in, sf_wire_out* out) {
         for (uint32_t s = 0; s <= S; s++) out->resp_off[s] = 0;
         return SF_OK;
     }
-    { int r2 = tok_ready(e); if (r2) return r2; }
+    SF_TRY(tok_ready(e));
     hipStream_t st = e->stream;
     WireBufs w{};
     w.n = n; w.S = S;
@@ -2652,8 +2570,8 @@ int sf_serve_frames(sf_engine* e, const sf_wire_batch* in, sf_wire_out* out) {
     { hipError_t qe = wire_query_temp(w.n_tiles, S, F, &tmp);
       if (qe != hipSuccess) return fail(SF_ERR_DEVICE, std::string("wire temp: ") + hipGetErrorString(qe)); }
     // one grow-only arena, 256-B aligned pieces
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + std::max<size_t>(bytes, 16)); return o; };
+    Layout L;
+    auto take = [&](size_t bytes) { return L.take(min16(bytes)); };
     const bool host_in = in->mem == SF_MEM_HOST;
     const size_t o_bytes = host_in ? take(n + 16) : 0, o_soff = host_in ? take((S + 1) * 8) : 0;
     const size_t o_exit = take((size_t)n * 4), o_tent = take((size_t)w.n_tiles * 4),
@@ -2666,13 +2584,8 @@ int sf_serve_frames(sf_engine* e, const sf_wire_batch* in, sf_wire_out* out) {
                  o_nv = take((size_t)F * 4), o_qnv = take(((size_t)F + 1) * 4), o_qpo = take(((size_t)F + 1) * 4),
                  o_rw = take((size_t)F * 4), o_resp = take((size_t)F * 16), o_sb = take(S),
                  o_crel = take((size_t)S * 8), o_tmp = take(tmp);
-    if (off > e->wire_bytes) {
-        if (e->wire_arena) hipFree(e->wire_arena);
-        e->wire_arena = nullptr; e->wire_bytes = 0;
-        HIP_TRY(hipMalloc(&e->wire_arena, off));
-        e->wire_bytes = off;
-    }
-    char* A = (char*)e->wire_arena;
+    SF_TRY(e->wire_arena.reserve(e->pool, L.size()));
+    char* A = e->wire_arena.at(0);
     if (host_in) {
         HIP_TRY(hipMemcpyAsync(A + o_bytes, in->bytes, n, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(A + o_soff, soff.data(), (S + 1) * 8, hipMemcpyHostToDevice, st));
@@ -2713,15 +2626,14 @@ int sf_serve_frames(sf_engine* e, const sf_wire_batch* in, sf_wire_out* out) {
     const uint32_t n_req = (uint32_t)(both >> 32), n_resp = (uint32_t)both;
     HIP_TRY(hipMemsetAsync(e->st.err, 0, sizeof(int32_t), st));
     if (n_req) {
-        int rc = tok_work_ensure(e, n_req);
-        if (rc) return fail(rc, "token work buffers");
+        SF_TRY(tok_work_ensure(e->tw, n_req, e->cfg.max_batch, tok_temp_query));
         le = wire_compact(w, nf, n_req, in->now_ms, st);
         if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("wire compact: ") + hipGetErrorString(le));
         TokBatch b{};
         b.n = n_req; b.flow_id = w.q_fid; b.count = w.q_cnt; b.flags = w.q_flags; b.ts = w.q_ts;
         b.ptag = w.q_tag; b.pbits = w.q_bits; b.poff = w.q_poff;
         TokOut o{w.r_status, w.r_rem, w.r_wait};
-        le = tok_launch(e->ts, e->tw, b, o, st);
+        le = tok_launch(e->ts, e->tw.w, b, o, st);
         if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("token launch: ") + hipGetErrorString(le));
     }
     le = wire_encode(w, nf, st);
@@ -2771,7 +2683,7 @@ int sf_cluster_sum(sf_engine* e, int64_t flow_id, int event, int64_t now_ms, int
 // ---------------------------------------------------------------- cluster concurrency tokens
 // state of the concurrency tokens present; caller holds e->mu
 static int cc_ready(sf_engine* e) {
-    { int r2 = tok_ready(e); if (r2) return r2; }
+    SF_TRY(tok_ready(e));
     if (!e->cc.cs.now || !e->cc.cs.cfg || !e->cc.cs.ctr) return cc_tables(e, nullptr);
     return SF_OK;
 }
@@ -2800,13 +2712,10 @@ static int cc_pool_ensure(sf_engine* e, uint64_t need_free, uint64_t min_cap) {
     if (ncap == cap) return SF_OK;
     hipStream_t s = e->stream;
     CcSlot* slots = nullptr; uint32_t* stack = nullptr; uint32_t* claim = nullptr;
-    hipError_t he = hipMalloc((void**)&slots, ncap * sizeof(CcSlot));
-    if (he == hipSuccess) he = hipMalloc((void**)&stack, ncap * 4);
-    if (he == hipSuccess) he = hipMalloc((void**)&claim, ncap * 4);
-    if (he != hipSuccess) {
-        for (void* p : {(void*)slots, (void*)stack, (void*)claim}) if (p) hipFree(p);
-        return fail(SF_ERR_NOMEM, std::string("concurrency token pool: ") + hipGetErrorString(he));
-    }
+    DevPool fresh{HIP_MEM};                    // (the new arrays; an early return frees them and the old pool stays)
+    SF_TRY(fresh.alloc(&slots, ncap * sizeof(CcSlot)));
+    SF_TRY(fresh.alloc(&stack, ncap * 4));
+    SF_TRY(fresh.alloc(&claim, ncap * 4));
     HIP_TRY(hipMemsetAsync(slots, 0, ncap * sizeof(CcSlot), s));
     if (cap) {
         HIP_TRY(hipMemcpyAsync(slots, cs.slots, cap * sizeof(CcSlot), hipMemcpyDeviceToDevice, s));
@@ -2814,30 +2723,12 @@ static int cc_pool_ensure(sf_engine* e, uint64_t need_free, uint64_t min_cap) {
         HIP_TRY(hipMemcpyAsync(claim, cs.claim, cap * 4, hipMemcpyDeviceToDevice, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
-    for (void* p : {(void*)cs.slots, (void*)cs.stack, (void*)cs.claim}) if (p) hipFree(p);
+    e->pool.release_all(cs.slots, cs.stack, cs.claim);
+    e->pool.adopt(fresh);
     cs.slots = slots; cs.stack = stack; cs.claim = claim; cs.cap = (uint32_t)ncap;
     HIP_TRY(cc_push_range(cs, (uint32_t)cap, (uint32_t)ncap, s));
     if (cap) c.grows++;
     return cc_read_counters(e);
-}
-
-static int cc_work_ensure(sf_engine* e, uint32_t n) {
-    CcWork& w = e->cc.w;
-    const uint32_t nf = (uint32_t)e->host_cflow.size();
-    if (n <= w.cap && nf <= w.nf_cap) return SF_OK;
-    const size_t N = std::max<uint32_t>(n, w.cap), F = std::max<uint32_t>({nf, w.nf_cap, 1u});
-    free_cc_work(w);
-    auto A = [&](void** p, size_t bytes) -> int { return hipMalloc(p, std::max<size_t>(bytes, 16)) != hipSuccess; };
-    int rc = 0;
-    rc |= A((void**)&w.key_in, N * 4); rc |= A((void**)&w.key_out, N * 4);
-    rc |= A((void**)&w.idx_in, N * 4); rc |= A((void**)&w.idx_out, N * 4);
-    rc |= A((void**)&w.delta, N * 4); rc |= A((void**)&w.rslot, N * 4);
-    rc |= A((void**)&w.seg_lo, F * 4); rc |= A((void**)&w.seg_hi, F * 4);
-    if (rc) return fail(SF_ERR_NOMEM, "concurrency work buffers");
-    HIP_TRY(cc_query_temp((uint32_t)N, &w.sort_bytes));
-    if (A(&w.sort_tmp, w.sort_bytes)) return fail(SF_ERR_NOMEM, "concurrency work buffers");
-    w.cap = (uint32_t)N; w.nf_cap = (uint32_t)F;
-    return SF_OK;
 }
 
 int sf_load_concurrent_config(sf_engine* e, const sf_concurrent_config* cfg, uint32_t n) {
@@ -2853,7 +2744,7 @@ int sf_load_concurrent_config(sf_engine* e, const sf_concurrent_config* cfg, uin
 int sf_concurrent_reserve(sf_engine* e, uint64_t tokens) {
     if (!e) return fail(SF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(e->mu);
-    { int r2 = cc_ready(e); if (r2) return r2; }
+    SF_TRY(cc_ready(e));
     return cc_pool_ensure(e, 0, std::max<uint64_t>(tokens, 1));
 }
 
@@ -2864,22 +2755,16 @@ int sf_request_concurrent(sf_engine* e, const sf_concurrent_batch* in, sf_concur
     if (e->cfg.shard_count > 255) return fail(SF_ERR_UNSUPPORTED, "concurrency tokens: at most 255 shards (token id layout)");
     std::lock_guard<std::mutex> lk(e->mu);
     const uint32_t n = in->n;
-    { int r2 = cc_ready(e); if (r2) return r2; }
-    { int r2 = cc_work_ensure(e, n); if (r2) return r2; }
-    { int r2 = cc_pool_ensure(e, n, 0); if (r2) return r2; }     // a slot for every request, before any state changes
+    SF_TRY(cc_ready(e));
+    SF_TRY(cc_work_ensure(e->cc.ws, n, (uint32_t)e->host_cflow.size(), cc_temp_query));
+    SF_TRY(cc_pool_ensure(e, n, 0));     // a slot for every request, before any state changes
     CcHost& c = e->cc;
     hipStream_t s = e->stream;
-    const size_t off_op = 0, off_id = align_up(off_op + n), off_cnt = align_up(off_id + (size_t)n * 8),
-                 off_cl = align_up(off_cnt + (size_t)n * 4), off_ts = align_up(off_cl + (size_t)n * 4),
-                 off_st = align_up(off_ts + (size_t)n * 8), off_tid = align_up(off_st + n),
-                 need = align_up(off_tid + (size_t)n * 8);
-    if (need > c.stage_bytes) {
-        if (c.stage) hipFree(c.stage);
-        c.stage = nullptr; c.stage_bytes = 0;
-        HIP_TRY(hipMalloc(&c.stage, need));
-        c.stage_bytes = need;
-    }
-    char* base = (char*)c.stage;
+    Layout L;
+    const size_t off_op = L.take(n), off_id = L.take((size_t)n * 8), off_cnt = L.take((size_t)n * 4);
+    const size_t off_cl = L.take((size_t)n * 4), off_ts = L.take((size_t)n * 8), off_st = L.take(n), off_tid = L.take((size_t)n * 8);
+    SF_TRY(c.stage.reserve(e->pool, L.size()));
+    char* base = c.stage.at(0);
     CcBatch b{};
     b.n = n;
     if (in->mem == SF_MEM_HOST) {
@@ -2897,7 +2782,7 @@ int sf_request_concurrent(sf_engine* e, const sf_concurrent_batch* in, sf_concur
     const bool host_out = out->mem == SF_MEM_HOST;
     CcOut o{host_out ? (int8_t*)(base + off_st) : out->status, host_out ? (int64_t*)(base + off_tid) : out->token_id};
     HIP_TRY(hipMemsetAsync(e->st.err, 0, sizeof(int32_t), s));
-    hipError_t le = cc_launch(e->ts, c.cs, c.w, b, o, s);
+    hipError_t le = cc_launch(e->ts, c.cs, c.ws.w, b, o, s);
     if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("concurrent launch: ") + hipGetErrorString(le));
     if (host_out) {
         HIP_TRY(hipMemcpyAsync(out->status, o.status, n, hipMemcpyDeviceToHost, s));
@@ -2905,7 +2790,7 @@ int sf_request_concurrent(sf_engine* e, const sf_concurrent_batch* in, sf_concur
     }
     int32_t err = 0;
     HIP_TRY(hipMemcpyAsync(&err, e->st.err, 4, hipMemcpyDeviceToHost, s));
-    { int r2 = cc_read_counters(e); if (r2) return r2; }
+    SF_TRY(cc_read_counters(e));
     if (err) return fail(err, err == SF_ERR_CAPACITY ? "concurrency token pool exhausted"
                                                      : "invalid concurrent batch (a request owned by another shard?)");
     return SF_OK;
@@ -2915,18 +2800,14 @@ int sf_concurrent_expire(sf_engine* e, int64_t now_ms, const uint8_t* client_onl
                          uint32_t* n_expired) {
     if (!e || (n_clients && !client_online)) return fail(SF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(e->mu);
-    { int r2 = cc_ready(e); if (r2) return r2; }
+    SF_TRY(cc_ready(e));
     CcHost& c = e->cc;
-    if (n_clients > c.online_bytes) {
-        if (c.online) hipFree(c.online);
-        c.online = nullptr; c.online_bytes = 0;
-        HIP_TRY(hipMalloc((void**)&c.online, n_clients));
-        c.online_bytes = n_clients;
-    }
-    if (n_clients) HIP_TRY(hipMemcpyAsync(c.online, client_online, n_clients, hipMemcpyHostToDevice, e->stream));
+    SF_TRY(c.online.reserve(e->pool, n_clients));
+    uint8_t* online = (uint8_t*)c.online.p;
+    if (n_clients) HIP_TRY(hipMemcpyAsync(online, client_online, n_clients, hipMemcpyHostToDevice, e->stream));
     const uint64_t before = c.ctr.expired;
-    HIP_TRY(cc_expire(e->ts, c.cs, now_ms, c.online, n_clients, e->stream));
-    { int r2 = cc_read_counters(e); if (r2) return r2; }
+    HIP_TRY(cc_expire(e->ts, c.cs, now_ms, online, n_clients, e->stream));
+    SF_TRY(cc_read_counters(e));
     if (n_expired) *n_expired = (uint32_t)(c.ctr.expired - before);
     return SF_OK;
 }
@@ -2937,7 +2818,7 @@ int sf_concurrent_now(sf_engine* e, int64_t flow_id, int64_t* now_calls) {
     if (flow_id > 0)
         for (size_t i = 0; i < e->host_cflow.size(); i++) {
             if (e->host_cflow[i].flow_id != flow_id) continue;
-            { int r2 = cc_ready(e); if (r2) return r2; }
+            SF_TRY(cc_ready(e));
             int32_t v = 0;
             HIP_TRY(hipStreamSynchronize(e->stream));
             HIP_TRY(hipMemcpy(&v, e->cc.cs.now + i, 4, hipMemcpyDeviceToHost));
@@ -2993,14 +2874,14 @@ int sf_comm_init(sf_engine* e, int nranks, int rank, const uint8_t* id, size_t l
     std::memcpy(uid.internal, id, NCCL_UNIQUE_ID_BYTES);
     ncclResult_t r = ncclCommInitRank(&e->comm, nranks, uid, rank);
     if (r != ncclSuccess) { e->comm = nullptr; return fail(SF_ERR_DEVICE, std::string("ncclCommInitRank: ") + ncclGetErrorString(r)); }
-    if (!e->agg) HIP_TRY(hipMalloc((void**)&e->agg, 4096 * sizeof(int64_t)));
+    if (!e->agg) SF_TRY(e->pool.alloc(&e->agg, 4096 * sizeof(int64_t)));
     return SF_OK;
 }
 
 int sf_set_report_entry_node(sf_engine* e, const sf_node_state* node) {
     if (!e) return fail(SF_ERR_INVALID, "null engine");
     std::lock_guard<std::mutex> lk(e->mu);
-    { const int rc = en_fence(e); if (rc) return rc; }
+    SF_TRY(en_fence(e));
     if (!node) { e->report_set = false; return SF_OK; }
     EntryNode& r = e->report;
     r = EntryNode{};
@@ -3016,7 +2897,7 @@ int sf_set_report_entry_node(sf_engine* e, const sf_node_state* node) {
 int sf_entry_node_allreduce(sf_engine* e, sf_node_state* out) {
     if (!e || !out) return fail(SF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(e->mu);
-    { const int rc = en_fence(e); if (rc) return rc; }
+    SF_TRY(en_fence(e));
     if (!e->comm) return fail(SF_ERR_INVALID, "sf_comm_init first");
     const int S = e->cfg.sample_count, nb = S + MINUTE;
     hipStream_t s = e->stream;
@@ -3025,11 +2906,10 @@ int sf_entry_node_allreduce(sf_engine* e, sf_node_state* out) {
     auto nc = [&](ncclResult_t r, const char* what) -> int {
         return r == ncclSuccess ? SF_OK : fail(SF_ERR_DEVICE, std::string(what) + ": " + ncclGetErrorString(r));
     };
-    int rc;
-    if ((rc = nc(ncclAllReduce(ws, gws, nb, ncclInt64, ncclMax, e->comm, s), "allreduce max"))) return rc;
+    SF_TRY(nc(ncclAllReduce(ws, gws, nb, ncclInt64, ncclMax, e->comm, s), "allreduce max"));
     HIP_TRY(launch_en_pack_vals(e->en, S, gws, vals, minrt, s));
-    if ((rc = nc(ncclAllReduce(vals, vals, (size_t)nb * 6 + 1, ncclInt64, ncclSum, e->comm, s), "allreduce sum"))) return rc;
-    if ((rc = nc(ncclAllReduce(minrt, minrt, nb, ncclInt64, ncclMin, e->comm, s), "allreduce min"))) return rc;
+    SF_TRY(nc(ncclAllReduce(vals, vals, (size_t)nb * 6 + 1, ncclInt64, ncclSum, e->comm, s), "allreduce sum"));
+    SF_TRY(nc(ncclAllReduce(minrt, minrt, nb, ncclInt64, ncclMin, e->comm, s), "allreduce min"));
     std::vector<int64_t> h_ws(nb), h_vals((size_t)nb * 6 + 1), h_min(nb);
     HIP_TRY(hipMemcpyAsync(h_ws.data(), gws, nb * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(h_vals.data(), vals, h_vals.size() * 8, hipMemcpyDeviceToHost, s));
@@ -3052,34 +2932,24 @@ int sf_entry_node_allreduce(sf_engine* e, sf_node_state* out) {
 
 int sf_device_alloc(sf_engine* e, size_t bytes, void** ptr) {
     if (!e || !ptr) return fail(SF_ERR_INVALID, "null argument");
-    HIP_TRY(hipMalloc(ptr, bytes ? bytes : 16));
     std::lock_guard<std::mutex> lk(e->mu);
-    e->user_allocs.push_back(*ptr);
-    return SF_OK;
+    return e->user_dev.alloc(ptr, nz(bytes));
 }
 int sf_device_free(sf_engine* e, void* ptr) {
     if (!e) return fail(SF_ERR_INVALID, "null engine");
     std::lock_guard<std::mutex> lk(e->mu);
-    auto it = std::find(e->user_allocs.begin(), e->user_allocs.end(), ptr);
-    if (it == e->user_allocs.end()) return fail(SF_ERR_INVALID, "pointer not from sf_device_alloc");
-    e->user_allocs.erase(it);
-    HIP_TRY(hipFree(ptr));
+    if (!ptr || !e->user_dev.release(ptr)) return fail(SF_ERR_INVALID, "pointer not from sf_device_alloc");
     return SF_OK;
 }
 int sf_host_alloc(sf_engine* e, size_t bytes, void** ptr) {
     if (!e || !ptr) return fail(SF_ERR_INVALID, "null argument");
-    HIP_TRY(hipHostMalloc(ptr, bytes ? bytes : 16, hipHostMallocDefault));
     std::lock_guard<std::mutex> lk(e->mu);
-    e->host_allocs.push_back(*ptr);
-    return SF_OK;
+    return e->user_host.alloc_host(ptr, nz(bytes));
 }
 int sf_host_free(sf_engine* e, void* ptr) {
     if (!e) return fail(SF_ERR_INVALID, "null engine");
     std::lock_guard<std::mutex> lk(e->mu);
-    auto it = std::find(e->host_allocs.begin(), e->host_allocs.end(), ptr);
-    if (it == e->host_allocs.end()) return fail(SF_ERR_INVALID, "pointer not from sf_host_alloc");
-    e->host_allocs.erase(it);
-    HIP_TRY(hipHostFree(ptr));
+    if (!ptr || !e->user_host.release(ptr)) return fail(SF_ERR_INVALID, "pointer not from sf_host_alloc");
     return SF_OK;
 }
 int sf_memcpy(sf_engine* e, void* dst, const void* src, size_t bytes, int kind) {
@@ -3127,15 +2997,11 @@ int sf_read_param_thread(sf_engine* e, uint32_t resource, int param_idx, uint8_t
     uint32_t l = 0;
     if (!local_of(e, resource, &l)) return fail(SF_ERR_INVALID, "resource outside this shard");
     std::lock_guard<std::mutex> g(e->mu);
-    { const int rc = drain(e); if (rc) return rc; }
-    long long* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, 8));
+    SF_TRY(drain(e));
     long long h = 0;
-    hipError_t he = launch_param_thread_read(e->st, l, param_idx, tag, bits, d, e->stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    hipFree(d);
-    if (he != hipSuccess) return fail(SF_ERR_DEVICE, std::string("param thread read: ") + hipGetErrorString(he));
+    SF_TRY(read_back(e, &h, 8, "param thread read", [&](void* d) {
+        return launch_param_thread_read(e->st, l, param_idx, tag, bits, (long long*)d, e->stream);
+    }));
     *out = h;
     return SF_OK;
 }
@@ -3143,15 +3009,11 @@ int sf_read_param_thread(sf_engine* e, uint32_t resource, int param_idx, uint8_t
 int sf_param_table_stats(sf_engine* e, uint64_t* used, uint64_t* capacity, uint32_t* max_probe) {
     if (!e || !used || !capacity || !max_probe) return fail(SF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> g(e->mu);
-    { const int rc = drain(e); if (rc) return rc; }
-    unsigned long long* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, 16));
+    SF_TRY(drain(e));
     unsigned long long h[2] = {0, 0};
-    hipError_t he = launch_param_stats(e->st, d, e->stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    hipFree(d);
-    if (he != hipSuccess) return fail(SF_ERR_DEVICE, std::string("param stats: ") + hipGetErrorString(he));
+    SF_TRY(read_back(e, h, 16, "param stats", [&](void* d) {
+        return launch_param_stats(e->st, (unsigned long long*)d, e->stream);
+    }));
     *used = h[0]; *capacity = e->st.pcap_mask + 1; *max_probe = (uint32_t)h[1];
     return SF_OK;
 }
@@ -3160,7 +3022,7 @@ int sf_heavy_profile_read(sf_engine* e, sf_heavy_profile* out, uint32_t cap, uin
     if (!e || !n_out || (cap && !out)) return fail(SF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> g(e->mu);
     uint32_t cnt[7] = {0, 0, 0, 0, 0, 0, 0}, nseg = 0;
-    { const int rc = drain(e); if (rc) return rc; }
+    SF_TRY(drain(e));
     const Work& lw = e->slot[e->last].w;
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream2));
@@ -3229,8 +3091,7 @@ static bool dg_rule_equal(const sf_degrade_rule& a, const sf_degrade_rule& b) {
 int sf_load_degrade_rules(sf_engine* e, const sf_degrade_rule* rules, uint32_t n, uint32_t* n_loaded) {
     if (!e || (n && !rules)) return fail(SF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(e->mu);
-    const int rc = drain(e);
-    if (rc) return rc;
+    SF_TRY(drain(e));
     // buildCircuitBreakers (DegradeRuleManager.java:236-265): valid rules, list order per resource.
     // Everything is built in locals first; the engine's tables are swapped only
     // after every check and allocation succeeded (a failed load keeps the old rules).
@@ -3291,23 +3152,17 @@ int sf_load_degrade_rules(sf_engine* e, const sf_degrade_rule* rules, uint32_t n
     uint32_t *d_rr = nullptr, *d_off = nullptr;
     DevBreakerRule* d_rules = nullptr;
     sf_breaker_state* d_st = nullptr;
-    auto release = [&]() {
-        void* p[] = {d_rr, d_off, d_rules, d_st};
-        for (void* x : p) if (x) hipFree(x);
-    };
-    if (dalloc((void**)&d_rr, (size_t)e->R * 4) || dalloc((void**)&d_off, off.size() * 4) ||
-        dalloc((void**)&d_rules, (size_t)nv * sizeof(DevBreakerRule)) ||
-        dalloc((void**)&d_st, (size_t)nv * sizeof(sf_breaker_state))) {
-        release();
-        return SF_ERR_NOMEM;
-    }
-    hipError_t he = hipMemcpy(d_rr, rr_of.data(), (size_t)e->R * 4, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice);
-    if (he == hipSuccess && nv) he = hipMemcpy(d_rules, dr.data(), (size_t)nv * sizeof(DevBreakerRule), hipMemcpyHostToDevice);
-    if (he == hipSuccess && nv) he = hipMemcpy(d_st, st.data(), (size_t)nv * sizeof(sf_breaker_state), hipMemcpyHostToDevice);
-    if (he != hipSuccess) { release(); return fail(SF_ERR_DEVICE, std::string("degrade rule upload: ") + hipGetErrorString(he)); }
-    void* dptrs[] = {(void*)e->dg.rr_of, (void*)e->dg.off, (void*)e->dg.rules, e->dg.state};
-    for (void* p : dptrs) if (p) hipFree(p);
+    DevPool fresh{HIP_MEM};                    // (the new tables, freed by an early return)
+    SF_TRY(fresh.alloc(&d_rr, nz((size_t)e->R * 4)));
+    SF_TRY(fresh.alloc(&d_off, nz(off.size() * 4)));
+    SF_TRY(fresh.alloc(&d_rules, nz((size_t)nv * sizeof(DevBreakerRule))));
+    SF_TRY(fresh.alloc(&d_st, nz((size_t)nv * sizeof(sf_breaker_state))));
+    HIP_TRY(hipMemcpy(d_rr, rr_of.data(), (size_t)e->R * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    if (nv) HIP_TRY(hipMemcpy(d_rules, dr.data(), (size_t)nv * sizeof(DevBreakerRule), hipMemcpyHostToDevice));
+    if (nv) HIP_TRY(hipMemcpy(d_st, st.data(), (size_t)nv * sizeof(sf_breaker_state), hipMemcpyHostToDevice));
+    e->pool.release_all(e->dg.rr_of, e->dg.off, e->dg.rules, e->dg.state);
+    e->pool.adopt(fresh);
     e->dg = DegradeDev{};
     e->dg.rr_of = d_rr; e->dg.off = d_off; e->dg.rules = d_rules; e->dg.state = d_st;
     e->dg.n_rres = n_rres;
@@ -3320,8 +3175,7 @@ int sf_load_degrade_rules(sf_engine* e, const sf_degrade_rule* rules, uint32_t n
     uint32_t kb = 1;
     while ((1ull << kb) <= n_rres) kb++;                        // keys 0..n_rres (n_rres = no breaker)
     e->dg.key_bits = kb;
-    e->dgw.sort_tmp_bytes = 0;                                  // re-sized for the new key width
-    if (e->dgw.sort_tmp) { hipFree(e->dgw.sort_tmp); e->dgw.sort_tmp = nullptr; }
+    dg_drop_sort_tmp(e->dgw);                                   // re-sized for the new key width
     {   // the routing summary reads dg_rr_of
         hipError_t re = launch_rdesc(e->st, e->stream);
         if (re == hipSuccess) re = hipStreamSynchronize(e->stream);
@@ -3331,55 +3185,15 @@ int sf_load_degrade_rules(sf_engine* e, const sf_degrade_rule* rules, uint32_t n
     return SF_OK;
 }
 
-static int dg_ensure(sf_engine* e, uint32_t n) {
-    DegradeWork& w = e->dgw;
-    if (n > w.cap) {
-        void* ptrs[] = {w.keys_in, w.keys_out, w.idx_in, w.idx_out, w.sev, w.inv};
-        for (void* p : ptrs) if (p) hipFree(p);
-        w.keys_in = w.keys_out = w.idx_in = w.idx_out = nullptr;
-        w.sev = nullptr;
-        w.inv = nullptr;
-        if (dalloc((void**)&w.keys_in, (size_t)n * 4) || dalloc((void**)&w.keys_out, (size_t)n * 4) ||
-            dalloc((void**)&w.idx_in, (size_t)n * 4) || dalloc((void**)&w.idx_out, (size_t)n * 4) ||
-            dalloc((void**)&w.sev, (size_t)n * sizeof(DgEv)) || dalloc((void**)&w.inv, (size_t)n * 4))
-            return SF_ERR_NOMEM;
-        w.cap = n;
-        if (w.sort_tmp) { hipFree(w.sort_tmp); w.sort_tmp = nullptr; }
-        w.sort_tmp_bytes = 0;
-    }
-    if (!w.sort_tmp) {
-        size_t bytes = 0;
-        HIP_TRY(dg_sort_bytes(w.cap, e->dg.key_bits, &bytes));
-        if (dalloc(&w.sort_tmp, bytes)) return SF_ERR_NOMEM;
-        w.sort_tmp_bytes = bytes;
-    }
-    if (e->dg.n_rres > w.beg_cap || !w.beg) {
-        if (w.beg) hipFree(w.beg);
-        if (w.end) hipFree(w.end);
-        if (w.heavy) hipFree(w.heavy);
-        w.beg = w.end = w.heavy = nullptr;
-        const uint32_t c = std::max<uint32_t>(e->dg.n_rres, 1);
-        if (dalloc((void**)&w.beg, (size_t)c * 4) || dalloc((void**)&w.end, (size_t)c * 4) ||
-            dalloc((void**)&w.heavy, (size_t)c * 4))
-            return SF_ERR_NOMEM;
-        w.beg_cap = c;
-    }
-    if (!w.err && dalloc((void**)&w.err, 4)) return SF_ERR_NOMEM;
-    if (!w.n_heavy && dalloc((void**)&w.n_heavy, 4)) return SF_ERR_NOMEM;
-    return SF_OK;
-}
-
 int sf_degrade_submit(sf_engine* e, const sf_event_batch* in, sf_verdicts* out) {
     if (!e || !in || !out || !out->status) return fail(SF_ERR_INVALID, "null argument");
     if (in->n == 0) return SF_OK;
     if (!in->res_id || !in->ts_ms || !in->flags) return fail(SF_ERR_INVALID, "missing event array");
     if (in->n > e->cfg.max_batch) return fail(SF_ERR_CAPACITY, "batch larger than max_batch");
     std::lock_guard<std::mutex> lk(e->mu);
-    int rc = drain(e);
-    if (rc) return rc;
+    SF_TRY(drain(e));
     const uint32_t n = in->n;
-    rc = dg_ensure(e, n);
-    if (rc) return rc;
+    SF_TRY(dg_work_ensure(e->dgw, n, e->dg.n_rres, e->dg.key_bits, dg_temp_query));
     hipStream_t s = e->stream;
     DegradeBatch b{};
     b.n = n; b.shard_count = e->cfg.shard_count; b.shard_index = e->cfg.shard_index; b.R = e->R;
@@ -3389,22 +3203,13 @@ int sf_degrade_submit(sf_engine* e, const sf_event_batch* in, sf_verdicts* out) 
     int32_t* wait = out->wait_ms;
     const bool host_in = in->mem == SF_MEM_HOST, host_out = out->mem == SF_MEM_HOST;
     if (host_in || host_out) {
-        size_t need = 0;
-        const size_t o_res = need; need += host_in ? align_up((size_t)n * 4) : 0;
-        const size_t o_ts = need; need += host_in ? align_up((size_t)n * 8) : 0;
-        const size_t o_fl = need; need += host_in ? align_up((size_t)n) : 0;
-        const size_t o_er = need; need += host_in && in->entry_ref ? align_up((size_t)n * 8) : 0;
-        const size_t o_ct = need; need += host_in && in->create_ts ? align_up((size_t)n * 8) : 0;
-        const size_t o_st = need; need += host_out ? align_up((size_t)n) : 0;
-        const size_t o_ru = need; need += host_out && rule ? align_up((size_t)n * 2) : 0;
-        const size_t o_wa = need; need += host_out && wait ? align_up((size_t)n * 4) : 0;
-        if (need > e->dg_stage_bytes) {
-            if (e->dg_stage) hipFree(e->dg_stage);
-            e->dg_stage = nullptr;
-            if (dalloc(&e->dg_stage, need)) return SF_ERR_NOMEM;
-            e->dg_stage_bytes = need;
-        }
-        char* base = (char*)e->dg_stage;
+        Layout L;
+        const size_t o_res = L.take_if(host_in, (size_t)n * 4), o_ts = L.take_if(host_in, (size_t)n * 8);
+        const size_t o_fl = L.take_if(host_in, n), o_er = L.take_if(host_in && in->entry_ref, (size_t)n * 8);
+        const size_t o_ct = L.take_if(host_in && in->create_ts, (size_t)n * 8), o_st = L.take_if(host_out, n);
+        const size_t o_ru = L.take_if(host_out && rule, (size_t)n * 2), o_wa = L.take_if(host_out && wait, (size_t)n * 4);
+        SF_TRY(e->dg_stage.reserve(e->pool, L.size()));
+        char* base = e->dg_stage.at(0);
         auto up = [&](size_t off, const void* src, size_t bytes) -> const void* {
             if (!src) return nullptr;
             hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, s);
@@ -3426,10 +3231,10 @@ int sf_degrade_submit(sf_engine* e, const sf_event_batch* in, sf_verdicts* out) 
     if (!host_in) {
         b.res = in->res_id; b.ts = in->ts_ms; b.flags = in->flags; b.eref = in->entry_ref; b.cts = in->create_ts;
     }
-    HIP_TRY(hipMemsetAsync(e->dgw.err, 0, 4, s));
-    HIP_TRY(dg_launch(e->dg, e->dgw, b, status, rule, wait, s));
+    HIP_TRY(hipMemsetAsync(e->dgw.w.err, 0, 4, s));
+    HIP_TRY(dg_launch(e->dg, e->dgw.w, b, status, rule, wait, s));
     int err = 0;
-    HIP_TRY(hipMemcpyAsync(&err, e->dgw.err, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&err, e->dgw.w.err, 4, hipMemcpyDeviceToHost, s));
     if (host_out) {
         HIP_TRY(hipMemcpyAsync(out->status, status, n, hipMemcpyDeviceToHost, s));
         if (rule) HIP_TRY(hipMemcpyAsync(out->rule_idx, rule, (size_t)n * 2, hipMemcpyDeviceToHost, s));

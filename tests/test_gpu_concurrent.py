@@ -123,6 +123,19 @@ def test_chunk_edges(eng_mod):
 
 
 @gpu
+def test_buffers_regrow(eng_mod):
+    """Batches of 3, 300 and 3 requests on one engine: the work set and the
+    staging buffer are built, grown and reused by a smaller batch."""
+    e, rp = pair(eng_mod, [cm.Rule(1, 120.0), cm.Rule(2, 7.0)])
+    rng = np.random.default_rng(3)
+    for k, n in enumerate((3, 300, 3)):
+        rows = [(cm.A, int(rng.integers(1, 3)), int(rng.integers(1, 4)), int(rng.integers(0, 4))) for _ in range(n)]
+        rp.run(cm.make_batch(rows, ts=1000 + k))
+    st = np.array(rp.status)
+    assert (st == cm.OK).sum() > 20 and (st == cm.BLOCKED).sum() > 20
+
+
+@gpu
 def test_malformed_releases(eng_mod):
     e, rp = pair(eng_mod, [cm.Rule(1, 100.0)])
     rp.run(cm.make_batch([(cm.A, 1, 1, 0)] * 4, ts=10))                      # requests 0..3 hold tokens

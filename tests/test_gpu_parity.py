@@ -25,6 +25,16 @@ def test_workload(eng_mod, so, name, heavy_min):
     workloads.run(eng_mod.FlowEngine, so.OracleEngine, w)
 
 
+def test_host_staging_regrows(eng_mod, so):
+    """Host batches of 3, 300 and 3 events on one engine (max_batch 400): the
+    staging buffers of sf_submit are built, grown and reused by a smaller batch."""
+    w = workloads.config3(R=40, n=306, seed=43, split=1, duration_ms=1500)
+    full = w["batches"][0]
+    w["batches"] = [full.subset(0, 3), full.subset(3, 303), full.subset(303, 306)]
+    w["cfg"].max_batch = 400
+    workloads.run(eng_mod.FlowEngine, so.OracleEngine, w)
+
+
 @pytest.mark.parametrize("heavy_min", [0, 64])
 def test_config3_many_batches(eng_mod, so, heavy_min):
     w = workloads.config3(R=20_000, n=600_000, seed=17, split=5)

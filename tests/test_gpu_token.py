@@ -28,15 +28,15 @@ def compare_tokens(got, want, what=""):
                              f"{want.wait_ms[i]})")
 
 
-def run_tokens(eng_mod, so, n_req, split=1, seed=5, max_qps=-1.0, check_sums=True, **kw):
+def run_tokens(eng_mod, so, n_req, split=1, seed=5, max_qps=-1.0, check_sums=True, cuts=None, max_batch=None, **kw):
     ns, flow, param, items, b = trace.token_workload(n_req, seed=seed, max_qps=max_qps, **kw)
-    cfg = abi.default_config(max_resources=4, max_batch=b.n, param_capacity=1 << 16)
+    cfg = abi.default_config(max_resources=4, max_batch=max_batch or b.n, param_capacity=1 << 16)
     e = eng_mod.FlowEngine(cfg)
     o = so.OracleEngine(cfg)
     for x in (e, o):
         x.load_namespaces(ns)
         x.load_cluster_rules(flow, param, items)
-    cuts = np.linspace(0, b.n, split + 1).astype(int)
+    cuts = np.linspace(0, b.n, split + 1).astype(int) if cuts is None else cuts
     for k, (lo, hi) in enumerate(zip(cuts[:-1], cuts[1:])):
         sub = abi.HostTokenBatch(b.flow_id[lo:hi], b.count[lo:hi], b.flags[lo:hi], b.ts_ms[lo:hi],
                                  param_tag=b.param_tag[lo:hi], param_bits=b.param_bits[lo:hi])
@@ -64,6 +64,13 @@ def test_token_server_namespace_limiter(eng_mod, so, max_qps):
 def test_token_server_heavy_values(eng_mod, so):
     """Few values, many requests each (long per-value chains) and all prioritized."""
     run_tokens(eng_mod, so, 50_000, split=2, seed=11, n_values=5, n_flow=5, n_param=3, prio_frac=1.0)
+
+
+def test_token_server_buffers_regrow(eng_mod, so):
+    """Batches of 3, 300 and 3 requests on one engine with max_batch 200: the
+    work set (sized for max_batch, then for the 300) and the staging buffer
+    are built, grown and reused by a smaller batch."""
+    run_tokens(eng_mod, so, 306, seed=17, cuts=[0, 3, 303, 306], max_batch=200)
 
 
 def test_token_server_bad_requests(eng_mod, so):
