@@ -289,9 +289,10 @@ SF_HD void heavy_qps(Team& tm, const DevState& st, const SegIO& io, const HeavyC
         if (has_entry) {
             const int64_t* pcg = hc.pcg;
             const int64_t pc0 = p ? pcg[p - 1] : 0;
-            // first failing entry: (double)(base + Σc[p..j]) > thr  (DefaultController: (int)passQps + c > count)
+            // first failing entry: !((double)(base + Σc[p..j]) <= thr)  (DefaultController: (int)passQps + c > count;
+            // a WarmUp rule of count 0 has a NaN threshold, 0 * inf, under which Java's <= lets nothing pass)
             const uint32_t f = team_first_true(tm, p, b, [&](uint32_t j) {
-                return (double)(base + (pcg[j] - pc0)) > thr;
+                return !((double)(base + (pcg[j] - pc0)) <= thr);
             });
             if (f > p) { passed = (f ? pcg[f - 1] : 0) - pc0; set_pass_range(tm, hc.passbits, p, f); }
             // tail: remaining entries with small acquireCount may still fit

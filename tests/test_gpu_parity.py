@@ -120,10 +120,14 @@ def test_heavy_thread_ms_blocks(eng_mod, so, seed):
 @pytest.mark.parametrize("count,rt_mean,duration", [(50.0, 5.0, 300), (3.0, 2.0, 300), (5000.0, 20.0, 300),
                                                    (400.0, 0.3, 150), (80.0, 200.0, 400)])
 def test_heavy_thread_runs(eng_mod, so, count, rt_mean, duration):
-    """The THREAD walk's run mode (chunks of a few long runs of entries and of
-    exits): saturated with a small and a tiny room, never saturated, exits in
-    their entry's millisecond, and exits far beyond the LDS ring (the HBM
-    live-exit bitmap) -- against the oracle, two batches."""
+    """The THREAD window walk's run step (thr_decide_runs: chunks of a few long
+    runs of entries and of exits): saturated with a small and a tiny room,
+    never saturated, exits in their entry's millisecond, and exits many events
+    ahead (at rt_mean 200 beyond the walk's LDS live-exit ring, in the HBM
+    bitmap) -- against the oracle, two batches.  The acquireCounts above 2^20
+    keep these segments out of THREAD run mode (thr_run_mode), and a batch has
+    at most 800 runs: its counter ring (RUN_RC runs ahead) and the run_pre
+    path beyond it are covered by tests/test_gpu_boundary.py (far_runs)."""
     workloads.run(eng_mod.FlowEngine, so.OracleEngine,
                   ms_block_thread_workload(7, n_entry=150_000, duration=duration, count=count, rt_mean=rt_mean))
 
