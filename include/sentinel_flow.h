@@ -197,9 +197,10 @@ typedef struct sf_system_rule {
 #define SF_EV_IN     0x02u   /* EntryType.IN (feeds ENTRY_NODE / SystemRule)   */
 #define SF_EV_PRIO   0x04u   /* prioritized entry                              */
 #define SF_EV_ERROR  0x08u   /* EXIT: business exception recorded (Tracer)     */
-/* ENTRY blocked by a slot that StatisticSlot wraps but the engine does not run
+/* ENTRY blocked by a slot that StatisticSlot wraps and the caller ran itself
  * (AuthoritySlot, order -6000, between StatisticSlot -7000 and SystemSlot
- * -5000: Constants.java:80-84).  StatisticSlot.entry catches its
+ * -5000: Constants.java:80-84; the engine runs it instead once rules are
+ * loaded with sf_load_authority_rules, below).  StatisticSlot.entry catches its
  * BlockException (AuthorityException) like any other (StatisticSlot.java:102-124):
  * block += count on the resource's ClusterNode and, for EntryType.IN, on
  * ENTRY_NODE; no SystemRule / ParamFlowRule / FlowRule / breaker sees the
@@ -892,6 +893,49 @@ typedef struct sf_breaker_state {  /* one circuit breaker after the last batch *
 int  sf_load_degrade_rules(sf_engine* e, const sf_degrade_rule* rules, uint32_t n, uint32_t* n_loaded);
 int  sf_degrade_submit(sf_engine* e, const sf_event_batch* in, sf_verdicts* out);
 int  sf_read_breaker(sf_engine* e, uint32_t breaker_index, sf_breaker_state* out);
+
+/* ---- AuthoritySlot black / white lists ---------------------------------------
+ * Replaces AuthoritySlot.checkBlackWhiteAuthority (AuthoritySlot.java:51-70)
+ * with AuthorityRuleChecker.passCheck (AuthorityRuleChecker.java:30-71) over
+ * the map AuthorityRuleManager.loadAuthorityConf builds (:108-139): at most one
+ * rule per resource, the first valid one in list order (a rule with a blank
+ * resource -- SF_REF_NONE --, strategy < 0 or a blank limitApp is ignored,
+ * isValidRule :147-150).  The caller splits limitApp at "," (String.split: no
+ * trimming, so "appB, appE" holds " appE") and interns each piece with the
+ * interner of the event origins; rule k's ids are apps[app_off .. app_off +
+ * app_cnt).  An entry with an empty origin (SF_ORIGIN_NONE) passes;
+ * SF_AUTHORITY_BLACK blocks an origin in the list, SF_AUTHORITY_WHITE one not
+ * in it, any other strategy value passes.
+ * With rules loaded, every submit path (sf_submit, sf_submit_async, the packed
+ * forms, sf_submit_node, sf_degrade_submit) decides a batch that carries
+ * origins as if each entry the rules block had been submitted with
+ * SF_EV_BLOCKED, except that its verdict is SF_V_BLOCK_AUTHORITY (rule_idx 0).
+ * A caller may still run the check itself and flag entries SF_EV_BLOCKED
+ * (verdict SF_V_BLOCK_OTHER); such an entry keeps that verdict whatever the
+ * loaded rules say.  The engine never writes the caller's arrays.  Flag bits
+ * 0x20 and 0x40 are reserved to the engine: set by a caller they are ignored.
+ * sf_load_authority_rules replaces the whole map (n == 0 clears it), ignores
+ * the rules of another shard, waits for the batches in flight, and on any
+ * failure leaves the old map in force; a rule whose app range leaves apps[]
+ * is SF_ERR_INVALID before anything is read.  *n_loaded (may be NULL) = rules
+ * kept on this shard.
+ * sf_authority_mark: out_flags[i] = flags[i] without the reserved bits, plus
+ * SF_EV_BLOCKED where the loaded rules block entry i -- for the protocols that
+ * plan on a merged host stream without origins (sf_system_plan,
+ * sf_submit_forced, sf_entry_node_add).  mem: SF_MEM_HOST or SF_MEM_DEVICE (all
+ * four arrays); origin NULL or no rules loaded: a copy.                      */
+#define SF_AUTHORITY_WHITE 0   /* RuleConstant.AUTHORITY_WHITE */
+#define SF_AUTHORITY_BLACK 1   /* RuleConstant.AUTHORITY_BLACK */
+#define SF_V_BLOCK_AUTHORITY 10   /* AuthorityException by a loaded rule; rule_idx 0 */
+typedef struct sf_authority_rule {
+    uint32_t resource;
+    int32_t  strategy;            /* as given; < 0 invalid, > 1 never blocks */
+    uint32_t app_off, app_cnt;    /* origin ids in apps[]; app_cnt 0 = blank limitApp: invalid */
+} sf_authority_rule;
+int  sf_load_authority_rules(sf_engine* e, const sf_authority_rule* rules, uint32_t n,
+                             const uint32_t* apps, uint32_t n_apps, uint32_t* n_loaded);
+int  sf_authority_mark(sf_engine* e, const uint32_t* res_id, const uint32_t* origin,
+                       const uint8_t* flags, uint32_t n, int mem, uint8_t* out_flags);
 
 /* ---- rule-list order (host only, no engine) -----------------------------
  * The order in which the reference's managers hold a resource's rules:

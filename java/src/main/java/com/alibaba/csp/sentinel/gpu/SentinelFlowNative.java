@@ -45,6 +45,12 @@ final class SentinelFlowNative {
             FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_DOUBLE, JAVA_DOUBLE));
     static final MethodHandle LOAD_DEGRADE = fn("sf_load_degrade_rules",
             FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS));
+    // AuthorityRuleManager.loadRules into the engine (the sf_authority_rule layout and the packer:
+    // AuthorityRuleTable); sf_authority_mark flags the entries the loaded rules block
+    static final MethodHandle LOAD_AUTHORITY = fn("sf_load_authority_rules",
+            FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS));
+    static final MethodHandle AUTHORITY_MARK = fn("sf_authority_mark",
+            FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, ADDRESS));
     // decisions
     static final MethodHandle SUBMIT = fn("sf_submit", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
     static final MethodHandle SUBMIT_PACKED = fn("sf_submit_packed",
@@ -174,7 +180,9 @@ final class SentinelFlowNative {
     // SF_EV_* / SF_V_* / SF_TOK_* / SF_TAG_* (sentinel_flow.h)
     static final byte EV_EXIT = 0x01, EV_IN = 0x02, EV_PRIO = 0x04, EV_ERROR = 0x08, EV_BLOCKED = 0x10;
     static final int V_PASS = 0, V_PASS_WAIT = 1, V_PRIORITY_WAIT = 2, V_BLOCK_FLOW = 3, V_BLOCK_PARAM = 4,
-            V_BLOCK_SYSTEM = 5, V_EXIT = 6, V_EXIT_IGNORED = 7, V_BLOCK_DEGRADE = 8, V_BLOCK_OTHER = 9;
+            V_BLOCK_SYSTEM = 5, V_EXIT = 6, V_EXIT_IGNORED = 7, V_BLOCK_DEGRADE = 8, V_BLOCK_OTHER = 9,
+            V_BLOCK_AUTHORITY = 10;
+    static final int AUTHORITY_WHITE = 0, AUTHORITY_BLACK = 1;
     static final byte TOK_PRIORITIZED = 0x01, TOK_PARAM = 0x02;
     static final byte TAG_NULL = 0, TAG_INT = 1, TAG_LONG = 2, TAG_STRING = 3, TAG_DOUBLE = 4, TAG_BOOL = 5,
             TAG_OTHER = 6, TAG_BYTE = 7, TAG_SHORT = 8, TAG_FLOAT = 9, TAG_COLLECTION = 0x40;

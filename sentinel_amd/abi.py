@@ -819,3 +819,27 @@ DEGRADE_RULE_DTYPE = np.dtype([(n, {C.c_uint32: "<u4", C.c_int32: "<i4", C.c_dou
 assert DEGRADE_RULE_DTYPE.itemsize == C.sizeof(sf_degrade_rule)
 
 STRUCT_SIZES.update({"sf_degrade_rule": C.sizeof(sf_degrade_rule), "sf_breaker_state": C.sizeof(sf_breaker_state)})
+
+# ---- AuthoritySlot black / white lists (include/sentinel_flow.h, sf_load_authority_rules) ----
+AUTHORITY_WHITE, AUTHORITY_BLACK = 0, 1      # RuleConstant.AUTHORITY_WHITE / AUTHORITY_BLACK
+V_BLOCK_AUTHORITY = 10       # entry blocked by a loaded AuthorityRule (AuthorityException); rule_idx 0
+
+
+class sf_authority_rule(C.Structure):
+    _fields_ = [("resource", C.c_uint32), ("strategy", C.c_int32), ("app_off", C.c_uint32), ("app_cnt", C.c_uint32)]
+
+
+def authority_tables(rules):
+    """``rules``: (resource id, strategy, [origin ids]) per AuthorityRule, in
+    list order; the ids are the pieces of limitApp split at "," and interned
+    like event origins.  Returns (sf_authority_rule array, apps uint32 array)."""
+    arr = (sf_authority_rule * max(len(rules), 1))()
+    apps = []
+    for k, (res, strategy, ids) in enumerate(rules):
+        arr[k].resource, arr[k].strategy = int(res), int(strategy)
+        arr[k].app_off, arr[k].app_cnt = len(apps), len(ids)
+        apps.extend(int(x) for x in ids)
+    return arr, np.asarray(apps, np.uint32)
+
+
+STRUCT_SIZES["sf_authority_rule"] = C.sizeof(sf_authority_rule)

@@ -621,13 +621,16 @@ SF_HD uint64_t param_run_rule(const ParamTable& pt, uint32_t res, int rule_k, co
 // offset of PV_DTS_FAR (65,535 ms or more) and a count field of 0 (a count
 // outside 1..255) read the caller's batch through the sort permutation.
 // ev_pack is the only encoder, the ev_* accessors below the only decoders.
-// sr: the planner's mask byte of the event (SYS_NONE: none).
-SF_HD uint32_t ev_pack(int64_t ts, int64_t ts0, uint8_t f, uint8_t sr, int32_t c) {
+// sr: the planner's mask byte of the event (SYS_NONE: none).  marked: f comes
+// from the effective-flags array of the AuthorityRule mark pass
+// (DevBatch::marked), where EVF_AUTH tells the engine's blocks from the
+// caller's; in a caller's own byte that bit is never read.
+SF_HD uint32_t ev_pack(int64_t ts, int64_t ts0, uint8_t f, uint8_t sr, int32_t c, bool marked = false) {
     const int64_t d = ts - ts0;
     const uint32_t dts = (d >= 0 && d < (int64_t)PV_DTS_FAR) ? (uint32_t)d : PV_DTS_FAR;
     uint32_t fl = f & 0x0Fu;
     if ((f & (SF_EV_BLOCKED | SF_EV_EXIT)) == SF_EV_BLOCKED)     // blocked by AuthoritySlot (before SystemSlot)
-        fl |= EVF_SYSBLK | ((uint32_t)SYSR_OTHER << EVF_SYSREASON_SHIFT);
+        fl |= EVF_SYSBLK | ((uint32_t)((marked && (f & EVF_AUTH)) ? SYSR_AUTH : SYSR_OTHER) << EVF_SYSREASON_SHIFT);
     else if ((f & SF_EV_IN) && !(f & SF_EV_EXIT) && sr < SYS_INERT)   // SystemBlockException forced by the planner
         fl |= EVF_SYSBLK | ((uint32_t)sr << EVF_SYSREASON_SHIFT);     // (SYS_INERT / SYS_NONE: none)
     const uint32_t c8 = (c >= 1 && c <= 255) ? (uint32_t)c : 0u;
@@ -782,16 +785,18 @@ SF_HD void nw_store_row(NodeWin<MAXS>& nd, const DevState& st, uint32_t res) {
 
 SF_HD bool v_blocked(uint8_t v) {
     return v == SF_V_BLOCK_FLOW || v == SF_V_BLOCK_PARAM || v == SF_V_BLOCK_SYSTEM || v == SF_V_BLOCK_DEGRADE ||
-           v == SF_V_BLOCK_OTHER;
+           v == SF_V_BLOCK_OTHER || v == SF_V_BLOCK_AUTHORITY;
 }
 // verdict of an entry carrying EVF_SYSBLK: a planned SystemBlockException
-// (reason 0..4 in rule_idx) or an SF_EV_BLOCKED entry (SYSR_OTHER)
+// (reason 0..4 in rule_idx), an SF_EV_BLOCKED entry (SYSR_OTHER) or one the
+// AuthorityRule mark pass blocked (SYSR_AUTH)
 SF_HD uint8_t sysblk_status(uint8_t fl) {
-    return ((fl >> EVF_SYSREASON_SHIFT) & 7) == SYSR_OTHER ? (uint8_t)SF_V_BLOCK_OTHER : (uint8_t)SF_V_BLOCK_SYSTEM;
+    const int r = (fl >> EVF_SYSREASON_SHIFT) & 7;
+    return r == SYSR_OTHER ? (uint8_t)SF_V_BLOCK_OTHER : r == SYSR_AUTH ? (uint8_t)SF_V_BLOCK_AUTHORITY : (uint8_t)SF_V_BLOCK_SYSTEM;
 }
 SF_HD int sysblk_rule(uint8_t fl) {
     const int r = (fl >> EVF_SYSREASON_SHIFT) & 7;
-    return r == SYSR_OTHER ? 0 : r;
+    return r == SYSR_OTHER || r == SYSR_AUTH ? 0 : r;
 }
 
 // the resource's circuit breakers [*b0, *b1) (DegradeRuleManager's list order)

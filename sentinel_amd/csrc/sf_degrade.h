@@ -112,6 +112,9 @@ struct DegradeBatch {
     const int64_t* eref; const int64_t* cts;
     uint32_t shard_count, shard_index, R;
     int64_t* last_ts;                          // engine clock (non-decreasing across batches)
+    // 1: flags is the engine's effective-flags array (AuthorityRule mark pass,
+    // sf_authority.h): bit 0x20 of a blocked entry says a loaded rule blocked it
+    uint8_t marked;
 };
 
 struct alignas(16) DgEv {                      // sorted event of a breaker resource, 32 B

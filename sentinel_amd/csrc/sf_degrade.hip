@@ -15,6 +15,7 @@
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 #include "sf_degrade.h"
+#include "sf_authority.h"
 
 namespace sf_dg {
 
@@ -42,7 +43,10 @@ __global__ void __launch_bounds__(BLK) k_dg_keys(DegradeDev d, DegradeBatch b, u
     bool skip = false;
     uint8_t st = (f & SF_EV_EXIT) ? SF_V_EXIT : SF_V_PASS;
     if (!(f & SF_EV_EXIT)) {
-        if (f & SF_EV_BLOCKED) { skip = true; st = SF_V_BLOCK_OTHER; }
+        if (f & SF_EV_BLOCKED) {
+            skip = true;
+            st = (b.marked && (f & sf::EVF_AUTH)) ? SF_V_BLOCK_AUTHORITY : SF_V_BLOCK_OTHER;
+        }
     } else if (b.eref) {
         const int64_t ref = b.eref[i];
         if (ref == -2 || (ref >= 0 && ref < (int64_t)i && (b.flags[ref] & (SF_EV_BLOCKED | SF_EV_EXIT)) == SF_EV_BLOCKED)) {

@@ -121,6 +121,10 @@ struct Slot {
     hipEvent_t evs[SF_NUM_EVENTS]{};   // fork / join and timing events of its batch
     PkStage pk;
     DevPool pkpool{HIP_MEM};        // owns the packed stage's buffers
+    // [max_batch] effective flags of its batch (the AuthorityRule mark pass,
+    // sf_authority.hip), in wpool; allocated once rules are loaded.  Read by
+    // the batch up to `end`.
+    uint8_t* aflags = nullptr;
 };
 
 struct sf_engine {
@@ -153,6 +157,7 @@ struct sf_engine {
     // rules
     std::vector<uint32_t> flow_pos;        // loaded valid rule index -> CSR position
     uint32_t n_flow = 0, n_prule = 0;
+    AuthTables auth{};                     // AuthorityRule tables in `pool` (auth.of null: no rule loaded)
     // the exact ParamFlow table's fill (param_reserve): inserts counted on the
     // device (st.pins), as of the last drain; upper bound of the inserts of
     // batches enqueued since; the most keys one event can insert
@@ -342,7 +347,7 @@ static int work_fill(sf_engine* e, Work& w, DevPool& m) {
 // (the slot is ready only with every buffer of its set; a failure leaves none)
 static int alloc_work(sf_engine* e, Slot& sl) {
     const int rc = work_fill(e, sl.w, sl.wpool);
-    if (rc) { sl.wpool.clear(); sl.w = Work{}; return rc; }
+    if (rc) { sl.wpool.clear(); sl.w = Work{}; sl.aflags = nullptr; return rc; }
     sl.ready = true;
     return SF_OK;
 }
@@ -946,6 +951,89 @@ int sf_set_system_status(sf_engine* e, double avg_load, double cpu_usage) {
     return SF_OK;
 }
 
+// ---------------------------------------------------------------- AuthorityRule (sf_authority.h)
+// the slot's effective-flags array, with its Work set's pool
+static int slot_aflags(sf_engine* e, Slot& sl) {
+    if (sl.aflags) return SF_OK;
+    return sl.wpool.alloc(&sl.aflags, nz(e->cfg.max_batch));
+}
+
+// AuthorityRuleManager.loadAuthorityConf: the new tables are built on the host
+// and in a scratch pool and adopted only when complete; until then the old map
+// stays in force.
+int sf_load_authority_rules(sf_engine* e, const sf_authority_rule* rules, uint32_t n, const uint32_t* apps,
+                            uint32_t n_apps, uint32_t* n_loaded) {
+    if (!e || (n && !rules)) return fail(SF_ERR_INVALID, "null argument");
+    for (uint32_t i = 0; i < n; i++)
+        if (rules[i].app_cnt && !apps) return fail(SF_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    SF_TRY(drain(e));   // pending batches were marked under the old rules
+    AuthHost h;
+    if (auth_build(rules, n, apps, n_apps, e->R, e->cfg.shard_count, e->cfg.shard_index, h) != SF_OK)
+        return fail(SF_ERR_INVALID, "authority rule: app range outside apps[], or a resource beyond max_resources");
+    AuthTables t{};
+    t.R = e->R; t.shard_count = e->cfg.shard_count; t.shard_index = e->cfg.shard_index;
+    DevPool fresh{HIP_MEM};                    // (the new tables, freed by an early return)
+    if (!h.rule.empty()) {
+        uint32_t *d_of = nullptr, *d_apps = nullptr;
+        AuthRule* d_rule = nullptr;
+        SF_TRY(fresh.alloc(&d_of, nz(h.of.size() * 4)));
+        SF_TRY(fresh.alloc(&d_rule, nz(h.rule.size() * sizeof(AuthRule))));
+        SF_TRY(fresh.alloc(&d_apps, nz(h.apps.size() * 4)));
+        HIP_TRY(hipMemcpy(d_of, h.of.data(), h.of.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_rule, h.rule.data(), h.rule.size() * sizeof(AuthRule), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_apps, h.apps.data(), h.apps.size() * 4, hipMemcpyHostToDevice));
+        for (Slot& sl : e->slot) SF_TRY(slot_aflags(e, sl));
+        t.of = d_of; t.rule = d_rule; t.apps = d_apps;
+    }
+    e->pool.release_all(e->auth.of, e->auth.rule, e->auth.apps);
+    e->pool.adopt(fresh);
+    e->auth = t;
+    if (n_loaded) *n_loaded = (uint32_t)h.rule.size();
+    return SF_OK;
+}
+
+// The mark pass of one batch on stream s, after its staging or expansion: with
+// rules loaded and origins in the batch, the slot's effective-flags array takes
+// the place of the batch's flags (whole batch, indexed like it, so planner
+// views, the degrade chain and the ENTRY_NODE update read it unchanged).  The
+// caller has ordered s after the `end` of the slot's previous batch.
+static int auth_apply(sf_engine* e, Slot& sl, DevBatch& b, hipStream_t s) {
+    if (!e->auth.of || !b.origin || !b.n) return SF_OK;
+    SF_TRY(slot_aflags(e, sl));
+    HIP_TRY(launch_auth_mark(e->auth, b.res, b.origin, b.flags, b.n, (uint8_t)(SF_EV_BLOCKED | EVF_AUTH), sl.aflags, s));
+    b.flags = sl.aflags;
+    b.marked = 1;
+    return SF_OK;
+}
+
+int sf_authority_mark(sf_engine* e, const uint32_t* res_id, const uint32_t* origin, const uint8_t* flags, uint32_t n,
+                      int mem, uint8_t* out_flags) {
+    if (!e || (n && (!res_id || !flags || !out_flags))) return fail(SF_ERR_INVALID, "null argument");
+    if (!n) return SF_OK;
+    std::lock_guard<std::mutex> lk(e->mu);
+    hipStream_t s = e->stream;
+    AuthTables t = e->auth;
+    if (!origin) { t.of = nullptr; origin = res_id; }          // nothing blocks: the ids are not compared
+    if (mem != SF_MEM_HOST) {
+        HIP_TRY(launch_auth_mark(t, res_id, origin, flags, n, (uint8_t)SF_EV_BLOCKED, out_flags, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return SF_OK;
+    }
+    DevPool tmp{HIP_MEM};
+    uint32_t *d_res = nullptr, *d_og = nullptr;
+    uint8_t *d_fl = nullptr, *d_out = nullptr;
+    SF_TRY(tmp.alloc(&d_res, (size_t)n * 4)); SF_TRY(tmp.alloc(&d_og, (size_t)n * 4));
+    SF_TRY(tmp.alloc(&d_fl, n)); SF_TRY(tmp.alloc(&d_out, n));
+    HIP_TRY(hipMemcpyAsync(d_res, res_id, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_og, origin, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_fl, flags, n, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_auth_mark(t, d_res, d_og, d_fl, n, (uint8_t)SF_EV_BLOCKED, d_out, s));
+    HIP_TRY(hipMemcpyAsync(out_flags, d_out, n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return SF_OK;
+}
+
 // The exact ParamFlow table never fills during a batch: before a batch with
 // ParamFlow rules, the keys it can insert at most ((events + collection
 // elements) x the most keys per event) must fit in the table's free half,
@@ -1185,8 +1273,9 @@ struct PackedHook { PreSort pre; bool acsr; uint32_t n_arg_events; };
 // safe sub-batches (sf_system.h), each planned on the exact ENTRY_NODE, then
 // sorted / decided / reduced by the ordinary pipeline.  One host round trip
 // per sub-batch (its end q).
-static int submit_sys_rounds(sf_engine* e, Slot& sl, const DevBatch& b, const DevVerdicts& dv, const sf_verdicts* out,
+static int submit_sys_rounds(sf_engine* e, Slot& sl, const DevBatch& staged, const DevVerdicts& dv, const sf_verdicts* out,
                              bool with_ox, const PreSort* pre) {
+    DevBatch b = staged;                                // (the mark pass below redirects its flags)
     const uint32_t n = b.n;
     hipStream_t s = e->stream, ss = e->serial ? e->stream : e->sstream;
     Work& w = sl.w;
@@ -1197,6 +1286,7 @@ static int submit_sys_rounds(sf_engine* e, Slot& sl, const DevBatch& b, const De
         const hipError_t pe = (*pre)(ss, w.err);
         if (pe != hipSuccess) return fail(SF_ERR_DEVICE, std::string("pre-sort: ") + hipGetErrorString(pe));
     }
+    SF_TRY(auth_apply(e, sl, b, ss));                   // before the planner: it skips marked IN entries
     HIP_TRY(hipEventRecord(sl.sorted, ss));
     HIP_TRY(hipStreamWaitEvent(s, sl.sorted, 0));
     SF_TRY(en_fence(e));
@@ -1268,13 +1358,15 @@ static int submit_core(sf_engine* e, const sf_event_batch* in, sf_verdicts* out,
     }
     if (e->sys.check && !forced) return submit_sys_rounds(e, sl, b, dv, out, with_ox, pre);
     // sort phase on the sort stream, into this batch's Work set (after the
-    // decide phase of the batch that used it last)
-    if (sl.used) HIP_TRY(hipStreamWaitEvent(ss, sl.done, 0));
+    // decide phase of the batch that used it last; the mark pass rewrites the
+    // flags that batch's ENTRY_NODE update reads)
+    if (sl.used) HIP_TRY(hipStreamWaitEvent(ss, e->auth.of && b.origin ? sl.end : sl.done, 0));
     HIP_TRY(hipMemsetAsync(w.err, 0, sizeof(int32_t), ss));
     if (pre) {
         const hipError_t pe = (*pre)(ss, w.err);
         if (pe != hipSuccess) return fail(SF_ERR_DEVICE, std::string("pre-sort: ") + hipGetErrorString(pe));
     }
+    SF_TRY(auth_apply(e, sl, b, ss));
     DevState stl = e->st;
     stl.err = w.err;
     hipError_t le = launch_sort(stl, w, b, e->cfg.shard_count, e->cfg.shard_index, e->key_bits, ss, sl.evs, e->timing);
@@ -1753,6 +1845,7 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
     DevBatch b{};
     DevVerdicts dv{};
     SF_TRY(stage_batch(e, in, out, s, b, dv));
+    SF_TRY(auth_apply(e, sl, b, s));             // this rank's own events, before the exchange sees them
     const int64_t* dseq = seq;
     if (in->mem == SF_MEM_HOST && n) {
         if (!e->sx_seq) SF_TRY(e->pool.alloc(&e->sx_seq, (size_t)e->cfg.max_batch * 8));
@@ -3202,12 +3295,16 @@ int sf_degrade_submit(sf_engine* e, const sf_event_batch* in, sf_verdicts* out) 
     uint16_t* rule = out->rule_idx;
     int32_t* wait = out->wait_ms;
     const bool host_in = in->mem == SF_MEM_HOST, host_out = out->mem == SF_MEM_HOST;
+    // AuthoritySlot precedes DegradeSlot: entries the loaded rules block are marked first
+    const bool auth = e->auth.of && in->origin;
+    const uint32_t* origin = in->origin;
     if (host_in || host_out) {
         Layout L;
         const size_t o_res = L.take_if(host_in, (size_t)n * 4), o_ts = L.take_if(host_in, (size_t)n * 8);
         const size_t o_fl = L.take_if(host_in, n), o_er = L.take_if(host_in && in->entry_ref, (size_t)n * 8);
         const size_t o_ct = L.take_if(host_in && in->create_ts, (size_t)n * 8), o_st = L.take_if(host_out, n);
         const size_t o_ru = L.take_if(host_out && rule, (size_t)n * 2), o_wa = L.take_if(host_out && wait, (size_t)n * 4);
+        const size_t o_og = L.take_if(host_in && auth, (size_t)n * 4);
         SF_TRY(e->dg_stage.reserve(e->pool, L.size()));
         char* base = e->dg_stage.at(0);
         auto up = [&](size_t off, const void* src, size_t bytes) -> const void* {
@@ -3221,6 +3318,7 @@ int sf_degrade_submit(sf_engine* e, const sf_event_batch* in, sf_verdicts* out) 
             b.flags = (const uint8_t*)up(o_fl, in->flags, n);
             b.eref = (const int64_t*)up(o_er, in->entry_ref, (size_t)n * 8);
             b.cts = (const int64_t*)up(o_ct, in->create_ts, (size_t)n * 8);
+            if (auth) origin = (const uint32_t*)up(o_og, in->origin, (size_t)n * 4);
         }
         if (host_out) {
             status = (uint8_t*)(base + o_st);
@@ -3230,6 +3328,13 @@ int sf_degrade_submit(sf_engine* e, const sf_event_batch* in, sf_verdicts* out) 
     }
     if (!host_in) {
         b.res = in->res_id; b.ts = in->ts_ms; b.flags = in->flags; b.eref = in->entry_ref; b.cts = in->create_ts;
+    }
+    if (auth) {                                  // (drained: the slot's array is free)
+        Slot& sl = e->slot[e->cur];
+        SF_TRY(slot_aflags(e, sl));
+        HIP_TRY(launch_auth_mark(e->auth, b.res, origin, b.flags, n, (uint8_t)(SF_EV_BLOCKED | EVF_AUTH), sl.aflags, s));
+        b.flags = sl.aflags;
+        b.marked = 1;
     }
     HIP_TRY(hipMemsetAsync(e->dgw.w.err, 0, 4, s));
     HIP_TRY(dg_launch(e->dg, e->dgw.w, b, status, rule, wait, s));

@@ -15,6 +15,7 @@
 
 #include "../../include/sentinel_flow.h"
 #include "sf_degrade.h"
+#include "sf_authority.h"
 
 namespace sf {
 
@@ -300,6 +301,10 @@ struct DevBatch {
     int64_t base;                  // index of the view's first event in the batch (0: whole batch)
     const uint8_t* sys;            // planner verdicts of IN entries (SYS_NONE: none), or null
     const uint8_t* vprev;          // verdicts of the batch (decided before the view), or null
+    // 1: flags is the slot's effective-flags array, written by the AuthorityRule
+    // mark pass (sf_authority.hip): EVF_AUTH is meaningful.  0: the caller's
+    // flags, whose bit 0x20 is never read.
+    uint8_t marked;
 };
 struct DevVerdicts { uint8_t* status; int32_t* wait; uint16_t* rule; };
 
@@ -316,6 +321,9 @@ constexpr uint8_t SYS_INERT = 0xFEu;
 // wraps but the engine does not run (AuthoritySlot), verdict SF_V_BLOCK_OTHER.
 // Like a SystemBlockException it is only a block count to every other slot.
 constexpr uint8_t SYSR_OTHER = 7;
+// ... of an entry the AuthorityRule mark pass blocked (SF_EV_BLOCKED | EVF_AUTH in
+// the effective flags): the same to every slot, verdict SF_V_BLOCK_AUTHORITY
+constexpr uint8_t SYSR_AUTH = 6;
 // sorted entry_ref of an exit whose entry was decided in an earlier sub-batch:
 // -1 it passed (the exit is live, like an entry of an earlier batch), -2 blocked
 constexpr int64_t EREF_DEAD = -2;
@@ -384,6 +392,9 @@ hipError_t launch_pk_args(const PkArgIn& in, const PkArgOut& out, const PkCopy& 
 // sf_sparse_verdicts: the nonzero waits / rule indices of n verdicts as (index << 32 | value) lists
 hipError_t launch_sparse_verdicts(const int32_t* wait, const uint16_t* rule, uint32_t n, unsigned long long* wl,
                                   unsigned long long* rl, uint32_t* counts, hipStream_t s);
+// AuthorityRule mark pass (sf_authority.hip): out[i] = auth_flag(flags[i]) with `mark` on blocked entries
+hipError_t launch_auth_mark(const AuthTables& t, const uint32_t* res, const uint32_t* origin, const uint8_t* flags,
+                            uint32_t n, uint8_t mark, uint8_t* out, hipStream_t s);
 // origin nodes (sf_origin.hip)
 hipError_t launch_ox_index(const DevState& st, Work& w, const DevBatch& b, uint32_t lim, hipStream_t s);
 hipError_t launch_ox_apply(const DevState& st, Work& w, const DevBatch& b, uint32_t n_heavy, uint32_t n_pairs,

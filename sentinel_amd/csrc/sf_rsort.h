@@ -44,7 +44,7 @@ constexpr uint32_t RS_MAX_CHUNKS = 1024;
 __device__ __forceinline__ uint32_t rs_meta(const DevBatch& b, uint32_t i, int64_t ts, int64_t ts0) {
     const uint8_t f = b.flags[i];
     const uint8_t sr = (b.sys && (f & SF_EV_IN) && !(f & SF_EV_EXIT)) ? b.sys[i] : SYS_NONE;
-    return ev_pack(ts, ts0, f, sr, b.cnt[i]);
+    return ev_pack(ts, ts0, f, sr, b.cnt[i], b.marked != 0);
 }
 
 __device__ __forceinline__ void rs_put_origin(uint32_t*, uint32_t, const PackedEv&) {}

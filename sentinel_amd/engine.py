@@ -100,6 +100,11 @@ def _declare(L):
     f("sf_load_degrade_rules", I, P, C.POINTER(abi.sf_degrade_rule), U32, C.POINTER(U32))
     f("sf_degrade_submit", I, P, C.POINTER(abi.sf_event_batch), C.POINTER(abi.sf_verdicts))
     f("sf_read_breaker", I, P, U32, C.POINTER(abi.sf_breaker_state))
+    # (an older tree's library selected by SENTINEL_FLOW_LIB -- the parent side of
+    # tools/authority_bench.py -- has neither; calling them there raises AttributeError)
+    if hasattr(L, "sf_load_authority_rules"):
+        f("sf_load_authority_rules", I, P, C.POINTER(abi.sf_authority_rule), U32, P, U32, C.POINTER(U32))
+        f("sf_authority_mark", I, P, P, P, P, U32, I, P)
     f("sf_snapshot", I, P, C.c_int64, C.POINTER(abi.sf_metric_row), U32, C.POINTER(U32))
     f("sf_load_resource_names", I, P, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), U32)
     f("sf_metric_log", I, P, C.c_int64, C.c_int64, I, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64),
@@ -342,6 +347,34 @@ class FlowEngine:
 
     def set_system_status(self, load, cpu):
         _check(lib().sf_set_system_status(self.h, load, cpu))
+
+    def load_authority_rules(self, rules) -> int:
+        """AuthorityRuleManager.loadRules: ``rules`` = (resource id, strategy,
+        [origin ids]) in list order (abi.authority_tables); an empty list clears
+        the map.  Returns the number of rules kept on this shard."""
+        arr, apps = abi.authority_tables(list(rules))
+        kept = C.c_uint32(0)
+        _check(lib().sf_load_authority_rules(self.h, arr, len(rules), apps.ctypes.data if apps.size else None,
+                                             apps.size, C.byref(kept)))
+        return int(kept.value)
+
+    def authority_mark(self, res_id, origin, flags) -> np.ndarray:
+        """sf_authority_mark on host arrays: ``flags`` with EV_BLOCKED added
+        where the loaded rules block the entry (origin None: a copy)."""
+        res = np.ascontiguousarray(res_id, np.uint32)
+        fl = np.ascontiguousarray(flags, np.uint8)
+        og = None if origin is None else np.ascontiguousarray(origin, np.uint32)
+        assert fl.shape == res.shape and (og is None or og.shape == res.shape)
+        out = np.empty_like(fl)
+        _check(lib().sf_authority_mark(self.h, res.ctypes.data, None if og is None else og.ctypes.data,
+                                       fl.ctypes.data, res.size, abi.MEM_HOST, out.ctypes.data))
+        return out
+
+    def authority_mark_device(self, res_id: "DeviceArray", origin: "DeviceArray", flags: "DeviceArray",
+                              out: "DeviceArray"):
+        """sf_authority_mark on HBM arrays (``out``: uint8 [n])."""
+        _check(lib().sf_authority_mark(self.h, res_id.ptr, None if origin is None else origin.ptr, flags.ptr,
+                                       int(np.prod(res_id.shape)), abi.MEM_DEVICE, out.ptr))
 
     def submit(self, batch: abi.HostBatch, out: abi.HostVerdicts = None) -> abi.HostVerdicts:
         out = abi.HostVerdicts(batch.n) if out is None else out

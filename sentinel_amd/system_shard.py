@@ -36,12 +36,15 @@ gather happens once per batch.  The verdicts equal those of one engine over
 the whole batch (tests/test_gpu_system_shard.py)."""
 from __future__ import annotations
 
+import copy
+
 import numpy as np
 
 from . import abi
 
 SYS_NONE = 0xFF
-_BLOCKED = (abi.V_BLOCK_FLOW, abi.V_BLOCK_PARAM, abi.V_BLOCK_SYSTEM, abi.V_BLOCK_DEGRADE, abi.V_BLOCK_OTHER)
+_BLOCKED = (abi.V_BLOCK_FLOW, abi.V_BLOCK_PARAM, abi.V_BLOCK_SYSTEM, abi.V_BLOCK_DEGRADE, abi.V_BLOCK_OTHER,
+            abi.V_BLOCK_AUTHORITY)
 
 
 def _blocked(v: np.ndarray) -> np.ndarray:
@@ -163,6 +166,16 @@ def submit_node_gather(eng, batch: abi.HostBatch, seq: np.ndarray, comm=None) ->
     n = batch.n
     seq = np.ascontiguousarray(seq, np.int64)
     assert seq.shape == (n,) and (n < 2 or (np.diff(seq) > 0).all())
+    # AuthoritySlot precedes SystemSlot: the merged stream and the sub-batches
+    # carry no origins, so this rank's entries that its loaded AuthorityRules
+    # block are flagged EV_BLOCKED here (sf_authority_mark) and get their
+    # verdict V_BLOCK_AUTHORITY back at the end
+    auth = np.zeros(n, bool)
+    if batch.origin is not None and n and hasattr(eng, "authority_mark"):
+        marked = eng.authority_mark(batch.res_id, batch.origin, batch.flags)
+        auth = ((marked & abi.EV_BLOCKED) != 0) & ((batch.flags & abi.EV_BLOCKED) == 0)
+        batch = copy.copy(batch)
+        batch.flags = marked
     fl = batch.flags
     is_in = (fl & abi.EV_IN) != 0
     li = np.nonzero(is_in)[0]
@@ -247,4 +260,5 @@ def submit_node_gather(eng, batch: abi.HostBatch, seq: np.ndarray, comm=None) ->
         eng.entry_node_add(seg, m_status[p:q])
         p = q
     decide_local(n, np.full(n - lp, SYS_NONE, np.uint8))    # no IN event on the node: nothing to plan
+    out.status[auth & (out.status == abi.V_BLOCK_OTHER)] = abi.V_BLOCK_AUTHORITY
     return out
