@@ -748,6 +748,89 @@ int  sf_serve_frames(sf_engine* e, const sf_wire_batch* in, sf_wire_out* out);
  * BLOCK_REQUEST 3, OCCUPIED_PASS 4, OCCUPIED_BLOCK 5, WAITING 6). */
 int  sf_cluster_sum(sf_engine* e, int64_t flow_id, int event, int64_t now_ms, int64_t* out);
 
+/* ---- Envoy rate-limit service (sentinel-cluster-server-envoy-rls) ---------
+ * sf_request_rls decides a batch of RateLimitRequests as
+ * SentinelEnvoyRlsServiceImpl.shouldRateLimit (v2 and v3 alike) would, on the
+ * cluster flow rules of sf_load_cluster_rules (EnvoyRlsRuleManager loads each
+ * descriptor as a GLOBAL flow rule with sampleCount 1; any loaded flow rule
+ * works).  The front-end keeps gRPC and protobuf and hands over the strings
+ * (domain, entry keys and values: indices into one string table) or, in the
+ * pre-hashed form (desc_flow_id != NULL), the flowId of every descriptor.
+ *   Order.  Descriptors are decided as if handed to the reference one by one
+ *     in (request, descriptor) order, at the request's ts_ms.  There is no
+ *     short-circuit: a descriptor after a blocked one still consumes.  Two
+ *     descriptors of one request with the same id are two consecutive
+ *     acquisitions.
+ *   Error requests.  hits_addend < 0 (the reference answers onError), or, in
+ *     the string form, any string of the request (its domain, any entry of any
+ *     of its descriptors) that is ill-formed UTF-8: an overlong form, a lone
+ *     or missing continuation byte, a sequence cut by the string's end, a code
+ *     point D800-DFFF or above 10FFFF, a byte F8-FF (the message would not have
+ *     parsed).  overall = SF_RLS_ERROR; its descriptors get code
+ *     SF_RLS_UNKNOWN, limit -1, remaining 0, flow_id -1; no counter moves.
+ *   Flow id.  key = domain, then "|" key "|" value per entry in entry order;
+ *     flowId = (long) Integer.MAX_VALUE + key.hashCode(), the hash taken over
+ *     the UTF-16 code units (a four-byte sequence contributes its two
+ *     surrogates); -1 when the key is blank: empty or made only of
+ *     Character.isWhitespace characters (the table is in sf_rls.h).
+ *     hits_addend == 0 counts as 1.
+ *   No rule (id <= 0, or no cluster *flow* rule of that id; a param rule does
+ *     not count): code OK, limit SF_RLS_NO_LIMIT, remaining 0, nothing counted.
+ *   With a rule (SimpleClusterFlowChecker): next = count * exceed_count -
+ *     avg(PASS) - hits.  next >= 0: PASS += hits, PASS_REQUEST += 1, code OK,
+ *     remaining (int) next; else BLOCK += hits, BLOCK_REQUEST += 1, code
+ *     OVER_LIMIT, remaining 0.  limit = (int) count.  The namespace limiter,
+ *     threshold_type and connected_count are never read; exceed_count is the
+ *     engine's.  overall is OVER_LIMIT iff a descriptor is not OK; a request
+ *     without descriptors is OK.
+ *   Shared state.  The ClusterMetric of a rule is the one sf_request_tokens,
+ *     sf_serve_frames and sf_cluster_sum use, under the same engine mutex and
+ *     stream (occupy state left by prioritized token requests transfers on the
+ *     next bucket roll here too).
+ *   Returns SF_ERR_UNSUPPORTED when shard_count != 1 (a request's descriptors
+ *     belong to several flowId owners; routing them is the front-end's job, as
+ *     for sf_serve_frames); SF_ERR_INVALID for malformed tables, with nothing
+ *     decided (desc_off[0] != 0, a decreasing desc_off / ent_off / str_off, a
+ *     string index >= n_str, a ts_ms < 0: times are epoch milliseconds, and a
+ *     negative one has no bucket window); SF_ERR_CAPACITY when n or n_desc exceeds
+ *     max_batch, or the strings hold 2^31 bytes or more.
+ * results: code is required; limit, remaining and flow_id may be NULL with
+ * SF_MEM_DEVICE.  sf_rls_flow_id is the flowId of one whole key (host only, no
+ * engine): -1 for a blank key, INT64_MIN for ill-formed UTF-8. */
+#define SF_RLS_UNKNOWN    0      /* RateLimitResponse.Code */
+#define SF_RLS_OK         1
+#define SF_RLS_OVER_LIMIT 2
+#define SF_RLS_ERROR      0xFF   /* overall[] only: onError, nothing checked */
+#define SF_RLS_NO_LIMIT   (-1)   /* limit[]: no rule, current_limit absent  */
+
+typedef struct sf_rls_batch {
+    uint32_t n; int32_t mem;            /* requests; SF_MEM_HOST / SF_MEM_DEVICE (all arrays) */
+    const int64_t*  ts_ms;              /* [n] server clock, >= 0, non-decreasing */
+    const int32_t*  hits_addend;        /* [n] */
+    const uint32_t* desc_off;           /* [n+1] descriptors of request i */
+    const int64_t*  desc_flow_id;       /* [n_desc] pre-hashed form, or NULL: */
+    const uint32_t* domain;             /* [n] string index */
+    const uint32_t* ent_off;            /* [n_desc+1] entries of descriptor d */
+    const uint32_t* ent_key, *ent_val;  /* [n_ent] string indices */
+    const uint32_t* str_off;            /* [n_str+1] byte offsets, total < 2^31 */
+    const uint8_t*  bytes;              /* UTF-8 */
+    uint32_t n_str;
+} sf_rls_batch;
+typedef struct sf_rls_results {
+    int32_t mem;
+    uint8_t* overall;                   /* [n] */
+    uint8_t* code;                      /* [n_desc] */
+    int32_t* limit, *remaining;         /* [n_desc] or NULL */
+    int64_t* flow_id;                   /* [n_desc] or NULL: the id that was looked up */
+} sf_rls_results;
+typedef struct sf_rls_stats {           /* summed since sf_create */
+    uint64_t requests, descriptors, error_requests, no_rule;
+    uint64_t segs_lane, segs_wave, chunks, chunks_serial, rounds;
+} sf_rls_stats;
+int     sf_request_rls(sf_engine* e, const sf_rls_batch* in, sf_rls_results* out);
+int     sf_rls_get_stats(sf_engine* e, sf_rls_stats* out);
+int64_t sf_rls_flow_id(const uint8_t* key_utf8, uint32_t len);  /* host only; INT64_MIN: ill-formed UTF-8 */
+
 /* State read-back and the per-second metric snapshot (StatisticNode.metrics). */
 int  sf_read_node(sf_engine* e, uint32_t resource, sf_node_state* out);
 int  sf_read_entry_node(sf_engine* e, sf_node_state* out);

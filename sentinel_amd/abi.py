@@ -843,3 +843,80 @@ def authority_tables(rules):
 
 
 STRUCT_SIZES["sf_authority_rule"] = C.sizeof(sf_authority_rule)
+
+
+# ---- Envoy rate-limit service (sf_request_rls)
+RLS_UNKNOWN, RLS_OK, RLS_OVER_LIMIT, RLS_ERROR, RLS_NO_LIMIT = 0, 1, 2, 0xFF, -1
+
+
+class sf_rls_batch(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("mem", C.c_int32), ("ts_ms", C.c_void_p), ("hits_addend", C.c_void_p),
+                ("desc_off", C.c_void_p), ("desc_flow_id", C.c_void_p), ("domain", C.c_void_p),
+                ("ent_off", C.c_void_p), ("ent_key", C.c_void_p), ("ent_val", C.c_void_p), ("str_off", C.c_void_p),
+                ("bytes", C.c_void_p), ("n_str", C.c_uint32)]
+
+
+class sf_rls_results(C.Structure):
+    _fields_ = [("mem", C.c_int32), ("overall", C.c_void_p), ("code", C.c_void_p), ("limit", C.c_void_p),
+                ("remaining", C.c_void_p), ("flow_id", C.c_void_p)]
+
+
+class sf_rls_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("requests", "descriptors", "error_requests", "no_rule", "segs_lane",
+                                          "segs_wave", "chunks", "chunks_serial", "rounds")]
+
+
+STRUCT_SIZES.update({"sf_rls_batch": C.sizeof(sf_rls_batch), "sf_rls_results": C.sizeof(sf_rls_results),
+                     "sf_rls_stats": C.sizeof(sf_rls_stats)})
+
+
+class HostRlsBatch:
+    """RateLimitRequests in host memory: the string form (domain / ent_* index
+    the string table str_off / data) or the pre-hashed form (desc_flow_id)."""
+
+    def __init__(self, ts_ms, hits_addend, desc_off, desc_flow_id=None, domain=None, ent_off=None, ent_key=None,
+                 ent_val=None, str_off=None, data=None):
+        self.ts_ms = np.ascontiguousarray(ts_ms, np.int64)
+        self.hits_addend = np.ascontiguousarray(hits_addend, np.int32)
+        self.desc_off = np.ascontiguousarray(desc_off, np.uint32)
+        self.n = self.ts_ms.shape[0]
+        assert self.desc_off.shape == (self.n + 1,)
+        self.n_desc = int(self.desc_off[-1])
+        self.desc_flow_id = None if desc_flow_id is None else np.ascontiguousarray(desc_flow_id, np.int64)
+        u32 = lambda a: None if a is None else np.ascontiguousarray(a, np.uint32)
+        self.domain, self.ent_off, self.ent_key, self.ent_val = u32(domain), u32(ent_off), u32(ent_key), u32(ent_val)
+        self.str_off = u32(str_off)
+        self.data = None if data is None else np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8))
+        self.n_str = 0 if self.str_off is None else self.str_off.shape[0] - 1
+
+    ARRAYS = ("ts_ms", "hits_addend", "desc_off", "desc_flow_id", "domain", "ent_off", "ent_key", "ent_val",
+              "str_off", "data")
+
+    def c_struct(self, ptr=None) -> sf_rls_batch:
+        """ptr: {array name: device address} for a batch in device memory."""
+        b = sf_rls_batch()
+        b.n, b.mem, b.n_str = self.n, MEM_HOST if ptr is None else MEM_DEVICE, self.n_str
+        for name in self.ARRAYS:
+            a = getattr(self, name)
+            field = "bytes" if name == "data" else name
+            setattr(b, field, None if a is None else (_ptr(a) if ptr is None else ptr[name]))
+        return b
+
+
+class HostRlsResults:
+    FIELDS = (("overall", np.uint8), ("code", np.uint8), ("limit", np.int32), ("remaining", np.int32),
+              ("flow_id", np.int64))
+
+    def __init__(self, n: int, n_desc: int):
+        self.overall = np.full(n, 0x7F, np.uint8)
+        self.code = np.full(n_desc, 0x7F, np.uint8)
+        self.limit = np.zeros(n_desc, np.int32)
+        self.remaining = np.zeros(n_desc, np.int32)
+        self.flow_id = np.zeros(n_desc, np.int64)
+
+    def c_struct(self) -> sf_rls_results:
+        r = sf_rls_results()
+        r.mem = MEM_HOST
+        for name, _ in self.FIELDS:
+            setattr(r, name, _ptr(getattr(self, name)))
+        return r

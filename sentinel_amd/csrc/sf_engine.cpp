@@ -23,6 +23,7 @@
 #include "sf_token.h"
 #include "sf_concur.h"
 #include "sf_wire.h"
+#include "sf_rls.h"
 #include "sf_degrade.h"
 #include "sf_mem.h"
 #include "sf_worksets.h"
@@ -180,6 +181,12 @@ struct sf_engine {
     CcHost cc;
     int64_t* d_sum = nullptr;
     GrowBuf wire_arena;                                  // sf_serve_frames scratch
+    // Envoy rate-limit service (sf_rls.hip): decided on ts / tw above
+    RlsWorkSet rlw{HIP_MEM};
+    GrowBuf rls_stage;
+    uint32_t* rls_len = nullptr;                         // [3] table lengths of a device-memory batch
+    uint32_t rls_wave_min = RLS_WAVE_MIN;                // diagnostics (SF_RLS_WAVE=0): every segment on the lane route
+    sf_rls_stats rls_stats{};
     // ENTRY_NODE and the metric snapshot (sf_entry.hip)
     EntryNode* en = nullptr;
     EntryAcc* en_acc = nullptr;
@@ -260,7 +267,7 @@ void sf_destroy(sf_engine* e) {
     if (!e) return;
     for (hipStream_t x : {e->sstream, e->stream, e->h2d, e->d2h}) if (x) hipStreamSynchronize(x);
     for (Slot& sl : e->slot) { sl.wpool.clear(); sl.pkpool.clear(); }
-    for (DevPool* p : {&e->pool, &e->user_dev, &e->user_host, &e->tw.pool, &e->cc.ws.pool, &e->dgw.pool, &e->ml_pool})
+    for (DevPool* p : {&e->pool, &e->user_dev, &e->user_host, &e->tw.pool, &e->rlw.pool, &e->cc.ws.pool, &e->dgw.pool, &e->ml_pool})
         p->clear();
     if (e->comm) ncclCommDestroy(e->comm);
     for (Slot& sl : e->slot) {
@@ -400,6 +407,7 @@ static int create(sf_engine* e) {
         else HIP_TRY(hipStreamCreateWithFlags(&e->sstream, hipStreamNonBlocking));
     }
     if (const char* v = getenv("SF_SERIAL_STREAMS")) e->serial = v[0] == '1';
+    if (const char* v = getenv("SF_RLS_WAVE")) if (v[0] == '0') e->rls_wave_min = UINT32_MAX;
     {   // the side stream of asynchronous batches: stream C, whose light lanes end
         // first (diagnostics SF_SIDE: 0 none -- on `stream` as before round 6 --,
         // 1 a stream of its own, 2 stream B, 3 stream C).  Same-box means of the
@@ -2770,6 +2778,127 @@ int sf_cluster_sum(sf_engine* e, int64_t flow_id, int event, int64_t now_ms, int
         HIP_TRY(hipStreamSynchronize(e->stream));
         return SF_OK;
     }
+    return SF_OK;
+}
+
+// ---------------------------------------------------------------- Envoy rate-limit service (sf_rls.h)
+int64_t sf_rls_flow_id(const uint8_t* key_utf8, uint32_t len) {
+    RlsKey k = rls_key_begin();
+    if (len) rls_key_feed(k, key_utf8, len);
+    return k.ok ? rls_key_id(k) : INT64_MIN;
+}
+
+int sf_rls_get_stats(sf_engine* e, sf_rls_stats* out) {
+    if (!e || !out) return fail(SF_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    *out = e->rls_stats;
+    return SF_OK;
+}
+
+int sf_request_rls(sf_engine* e, const sf_rls_batch* in, sf_rls_results* out) {
+    if (!e || !in || !out) return fail(SF_ERR_INVALID, "null argument");
+    if (e->cfg.shard_count != 1)
+        return fail(SF_ERR_UNSUPPORTED, "sf_request_rls on a sharded token server: route the descriptors by flowId");
+    const uint32_t n = in->n;
+    if (n == 0) return SF_OK;
+    if (!in->ts_ms || !in->hits_addend || !in->desc_off || !out->overall) return fail(SF_ERR_INVALID, "missing request array");
+    const bool strings = in->desc_flow_id == nullptr;
+    if (strings && (!in->domain || !in->ent_off || !in->str_off)) return fail(SF_ERR_INVALID, "missing string table");
+    const bool host_in = in->mem == SF_MEM_HOST, host_out = out->mem == SF_MEM_HOST;
+    if (n > e->cfg.max_batch) return fail(SF_ERR_CAPACITY, "more requests than max_batch");
+    std::lock_guard<std::mutex> lk(e->mu);
+    RlsBatch b{};
+    b.n = n; b.n_str = strings ? in->n_str : 0;
+    // the lengths of the tables are their last offsets: read in place, or gathered on the device for one copy
+    if (host_in) {
+        b.n_desc = in->desc_off[n];
+        if (strings && b.n_desc <= e->cfg.max_batch) { b.n_ent = in->ent_off[b.n_desc]; b.n_bytes = in->str_off[b.n_str]; }
+    } else {
+        if (!e->rls_len) SF_TRY(e->pool.alloc(&e->rls_len, 16));
+        b.desc_off = in->desc_off; b.desc_fid = in->desc_flow_id; b.ent_off = in->ent_off; b.str_off = in->str_off;
+        uint32_t len[3] = {0, 0, 0};
+        HIP_TRY(rls_lengths(b, e->rls_len, e->stream));
+        HIP_TRY(hipMemcpyAsync(len, e->rls_len, sizeof len, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        b.n_desc = len[0]; b.n_ent = len[1]; b.n_bytes = len[2];
+    }
+    if (b.n_desc > e->cfg.max_batch) return fail(SF_ERR_CAPACITY, "more descriptors than max_batch");
+    if (b.n_desc && !out->code) return fail(SF_ERR_INVALID, "null code array");
+    if (strings) {
+        if (b.n_bytes >= (1u << 31)) return fail(SF_ERR_CAPACITY, "rls strings must be < 2^31 bytes");
+        if ((b.n_ent && (!in->ent_key || !in->ent_val)) || (b.n_bytes && !in->bytes)) return fail(SF_ERR_INVALID, "missing string table");
+    }
+    const size_t nd = b.n_desc, ne = b.n_ent, ns = b.n_str;
+    SF_TRY(tok_work_ensure(e->tw, std::max(b.n_desc, 1u), e->cfg.max_batch, tok_temp_query));
+    SF_TRY(rls_work_ensure(e->rlw, std::max(n, b.n_desc), e->cfg.max_batch));
+    SF_TRY(tok_ready(e));
+    hipStream_t s = e->stream;
+    // staging: inputs (host form) then outputs (host results), 256-B aligned
+    Layout L;
+    const size_t o_ts = L.take_if(host_in, (size_t)n * 8), o_hits = L.take_if(host_in, (size_t)n * 4),
+                 o_doff = L.take_if(host_in, ((size_t)n + 1) * 4), o_fid = L.take_if(host_in && !strings, nd * 8),
+                 o_dom = L.take_if(host_in && strings, (size_t)n * 4), o_eoff = L.take_if(host_in && strings, (nd + 1) * 4),
+                 o_ek = L.take_if(host_in && strings, ne * 4), o_ev = L.take_if(host_in && strings, ne * 4),
+                 o_soff = L.take_if(host_in && strings, (ns + 1) * 4), o_bytes = L.take_if(host_in && strings, b.n_bytes);
+    const size_t r_all = L.take_if(host_out, n), r_code = L.take_if(host_out, nd), r_lim = L.take_if(host_out, nd * 4),
+                 r_rem = L.take_if(host_out, nd * 4), r_fid = L.take_if(host_out, nd * 8);
+    SF_TRY(e->rls_stage.reserve(e->pool, std::max<size_t>(L.size(), 16)));
+    char* base = e->rls_stage.at(0);
+    if (host_in) {
+        auto up = [&](size_t off, const void* src, size_t bytes) -> int {
+            if (bytes) HIP_TRY(hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, s));
+            return SF_OK;
+        };
+        SF_TRY(up(o_ts, in->ts_ms, (size_t)n * 8)); SF_TRY(up(o_hits, in->hits_addend, (size_t)n * 4));
+        SF_TRY(up(o_doff, in->desc_off, ((size_t)n + 1) * 4));
+        b.ts = (const int64_t*)(base + o_ts); b.hits = (const int32_t*)(base + o_hits);
+        b.desc_off = (const uint32_t*)(base + o_doff);
+        if (!strings) {
+            SF_TRY(up(o_fid, in->desc_flow_id, nd * 8));
+            b.desc_fid = (const int64_t*)(base + o_fid);
+        } else {
+            SF_TRY(up(o_dom, in->domain, (size_t)n * 4)); SF_TRY(up(o_eoff, in->ent_off, (nd + 1) * 4));
+            SF_TRY(up(o_ek, in->ent_key, ne * 4)); SF_TRY(up(o_ev, in->ent_val, ne * 4));
+            SF_TRY(up(o_soff, in->str_off, (ns + 1) * 4)); SF_TRY(up(o_bytes, in->bytes, b.n_bytes));
+            b.domain = (const uint32_t*)(base + o_dom); b.ent_off = (const uint32_t*)(base + o_eoff);
+            b.ent_key = (const uint32_t*)(base + o_ek); b.ent_val = (const uint32_t*)(base + o_ev);
+            b.str_off = (const uint32_t*)(base + o_soff); b.bytes = (const uint8_t*)(base + o_bytes);
+        }
+    } else {
+        b.ts = in->ts_ms; b.hits = in->hits_addend; b.desc_off = in->desc_off; b.desc_fid = in->desc_flow_id;
+        b.domain = in->domain; b.ent_off = in->ent_off; b.ent_key = in->ent_key; b.ent_val = in->ent_val;
+        b.str_off = in->str_off; b.bytes = in->bytes;
+    }
+    RlsOut o{};
+    if (host_out) {
+        o.overall = (uint8_t*)(base + r_all); o.code = (uint8_t*)(base + r_code); o.limit = (int32_t*)(base + r_lim);
+        o.remaining = (int32_t*)(base + r_rem); o.flow_id = (int64_t*)(base + r_fid);
+    } else {
+        o.overall = out->overall; o.code = out->code; o.limit = out->limit; o.remaining = out->remaining; o.flow_id = out->flow_id;
+    }
+    HIP_TRY(hipMemsetAsync(e->st.err, 0, sizeof(int32_t), s));
+    hipError_t le = rls_launch(e->ts, e->tw.w, e->rlw.w, b, o, e->rls_wave_min, s);
+    if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("rls launch: ") + hipGetErrorString(le));
+    int32_t err = 0;
+    RlsCounters c{};
+    HIP_TRY(hipMemcpyAsync(&err, e->st.err, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&c, e->rlw.w.ctr, sizeof c, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (err) return fail(err, "malformed rls batch (offsets must not decrease, string indices must be < n_str, ts_ms must be >= 0)");
+    if (host_out) {
+        HIP_TRY(hipMemcpyAsync(out->overall, o.overall, n, hipMemcpyDeviceToHost, s));
+        if (nd) {
+            HIP_TRY(hipMemcpyAsync(out->code, o.code, nd, hipMemcpyDeviceToHost, s));
+            if (out->limit) HIP_TRY(hipMemcpyAsync(out->limit, o.limit, nd * 4, hipMemcpyDeviceToHost, s));
+            if (out->remaining) HIP_TRY(hipMemcpyAsync(out->remaining, o.remaining, nd * 4, hipMemcpyDeviceToHost, s));
+            if (out->flow_id) HIP_TRY(hipMemcpyAsync(out->flow_id, o.flow_id, nd * 8, hipMemcpyDeviceToHost, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    sf_rls_stats& st = e->rls_stats;
+    st.requests += n; st.descriptors += nd; st.error_requests += c.error_requests; st.no_rule += c.no_rule;
+    st.segs_lane += c.segs_lane; st.segs_wave += c.segs_wave; st.chunks += c.chunks;
+    st.chunks_serial += c.chunks_serial; st.rounds += c.rounds;
     return SF_OK;
 }
 

@@ -54,6 +54,7 @@ struct CpSlot {                  // (param rule, value): one value's column of C
     int64_t cnt[CL_MAXS];
 };
 constexpr uint64_t CP_CLAIM = 1ull << 63;
+constexpr uint64_t KEY_NONE = ~0ull;          // sort key of a request that reached no checker (sorted last)
 
 struct TokState {
     uint32_t n_flow, n_rules, n_ns;
@@ -82,6 +83,57 @@ __device__ __forceinline__ int32_t id_lookup(const TokState& ts, int64_t id, boo
     }
     return -1;
 }
+
+// ---------------------------------------------------------------- ClusterMetric (one flowId, in LDS)
+struct ClMetric {
+    ClFlowState* s;
+    int S, wl, I;
+    double isec;
+    // LeapArray.currentWindow(t) with ClusterMetricLeapArray.resetWindowTo (:45-71); -1: throwaway
+    __device__ int cur(int64_t t) {
+        const int idx = (int)((t / wl) % S);
+        const int64_t ws = t - t % wl;
+        ClBucket& b = s->b[idx];
+        if (b.ws == WS_NONE) {                                   // newEmptyBucket: no transfer
+            b.ws = ws;
+            for (int k = 0; k < CE_COUNT; k++) b.c[k] = 0;
+            return idx;
+        }
+        if (b.ws == ws) return idx;
+        if (ws > b.ws) {
+            b.ws = ws;
+            for (int k = 0; k < CE_COUNT; k++) b.c[k] = 0;
+            if (s->has_occ) {                                    // transferOccupyToBucket :54-60
+                b.c[CE_OCCUPIED_PASS] = wadd(b.c[CE_OCCUPIED_PASS], s->occ_pass);
+                b.c[CE_PASS] = wadd(b.c[CE_PASS], s->occ_pass); s->occ_pass = 0;
+                b.c[CE_PASS_REQUEST] = wadd(b.c[CE_PASS_REQUEST], s->occ_req); s->occ_req = 0;
+                s->has_occ = 0;
+            }
+            return idx;
+        }
+        return -1;
+    }
+    __device__ int64_t sum(int ev, int64_t t) {                  // ClusterMetric.getSum :47-55
+        cur(t);
+        int64_t r = 0;
+        for (int k = 0; k < S; k++) {
+            const ClBucket& b = s->b[k];
+            if (b.ws != WS_NONE && !(wsub(t, b.ws) > I)) r = wadd(r, b.c[ev]);
+        }
+        return r;
+    }
+    __device__ double avg(int ev, int64_t t) { return (double)sum(ev, t) / isec; }
+    __device__ void add(int ev, int64_t n, int64_t t) {
+        const int k = cur(t);
+        if (k >= 0) s->b[k].c[ev] = wadd(s->b[k].c[ev], n);
+    }
+    __device__ int64_t head_pass(int64_t t) {                    // getFirstCountOfWindow -> getValidHead
+        const int idx = (int)(((t + wl) / wl) % S);
+        const ClBucket& b = s->b[idx];
+        if (b.ws == WS_NONE || wsub(t, b.ws) > I) return 0;
+        return b.c[CE_PASS];
+    }
+};
 #endif
 
 struct TokBatch {
@@ -107,6 +159,8 @@ struct TokWork {                 // sized for cfg.max_batch requests
 
 hipError_t tok_query_temp(uint32_t max_n, size_t* sort8, size_t* sort64, size_t* scan);
 hipError_t tok_launch(const TokState& ts, TokWork& w, const TokBatch& b, const TokOut& out, hipStream_t s);
+// the sort and segment table of tok_launch on keys the caller wrote (sf_rls.hip)
+hipError_t tok_sort_segments(TokWork& w, uint32_t n, unsigned end_bit, hipStream_t s);
 hipError_t tok_init_flow_state(ClFlowState* fs, uint32_t n, hipStream_t s);
 // ClusterMetric.getSum(event) at time now (rolls the current window like the reference)
 hipError_t tok_cluster_sum(const TokState& ts, uint32_t rule, int event, int64_t now, int64_t* d_out, hipStream_t s);

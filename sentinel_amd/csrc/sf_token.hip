@@ -33,7 +33,6 @@
 namespace sf {
 
 constexpr uint8_t NS_NONE = 0xff;
-constexpr uint64_t KEY_NONE = ~0ull;
 constexpr uint64_t KEY_PARAM = 1ull << 63;
 constexpr uint64_t KEY_SERIAL = 1ull << 62;     // every request of one param rule, in time order
 constexpr int8_t TOK_PENDING = 100;
@@ -221,57 +220,6 @@ __global__ void k_tok_segments(const uint64_t* key, const uint32_t* head, const 
     const bool last_valid = key[j] != KEY_NONE && (j == n - 1 || key[j + 1] == KEY_NONE);
     if (last_valid) { const uint32_t ns = pos[j] + head[j]; *n_seg = ns; seg_start[ns] = j + 1; }
 }
-
-// ---------------------------------------------------------------- ClusterMetric (one flowId, in LDS)
-struct ClMetric {
-    ClFlowState* s;
-    int S, wl, I;
-    double isec;
-    // LeapArray.currentWindow(t) with ClusterMetricLeapArray.resetWindowTo (:45-71); -1: throwaway
-    __device__ int cur(int64_t t) {
-        const int idx = (int)((t / wl) % S);
-        const int64_t ws = t - t % wl;
-        ClBucket& b = s->b[idx];
-        if (b.ws == WS_NONE) {                                   // newEmptyBucket: no transfer
-            b.ws = ws;
-            for (int k = 0; k < CE_COUNT; k++) b.c[k] = 0;
-            return idx;
-        }
-        if (b.ws == ws) return idx;
-        if (ws > b.ws) {
-            b.ws = ws;
-            for (int k = 0; k < CE_COUNT; k++) b.c[k] = 0;
-            if (s->has_occ) {                                    // transferOccupyToBucket :54-60
-                b.c[CE_OCCUPIED_PASS] = wadd(b.c[CE_OCCUPIED_PASS], s->occ_pass);
-                b.c[CE_PASS] = wadd(b.c[CE_PASS], s->occ_pass); s->occ_pass = 0;
-                b.c[CE_PASS_REQUEST] = wadd(b.c[CE_PASS_REQUEST], s->occ_req); s->occ_req = 0;
-                s->has_occ = 0;
-            }
-            return idx;
-        }
-        return -1;
-    }
-    __device__ int64_t sum(int ev, int64_t t) {                  // ClusterMetric.getSum :47-55
-        cur(t);
-        int64_t r = 0;
-        for (int k = 0; k < S; k++) {
-            const ClBucket& b = s->b[k];
-            if (b.ws != WS_NONE && !(wsub(t, b.ws) > I)) r = wadd(r, b.c[ev]);
-        }
-        return r;
-    }
-    __device__ double avg(int ev, int64_t t) { return (double)sum(ev, t) / isec; }
-    __device__ void add(int ev, int64_t n, int64_t t) {
-        const int k = cur(t);
-        if (k >= 0) s->b[k].c[ev] = wadd(s->b[k].c[ev], n);
-    }
-    __device__ int64_t head_pass(int64_t t) {                    // getFirstCountOfWindow -> getValidHead
-        const int idx = (int)(((t + wl) / wl) % S);
-        const ClBucket& b = s->b[idx];
-        if (b.ws == WS_NONE || wsub(t, b.ws) > I) return 0;
-        return b.c[CE_PASS];
-    }
-};
 
 // ClusterFlowChecker.acquireClusterToken (:55-112) for one request that passed the namespace gate
 __device__ void flow_decide(ClMetric& m, const ClRule& r, const TokState& ts, int32_t connected, int64_t t, int32_t c,
@@ -469,6 +417,24 @@ hipError_t tok_query_temp(uint32_t max_n, size_t* sort8, size_t* sort64, size_t*
                                    rocprim::plus<uint32_t>());
 }
 
+// (key_in, idx_in) -> key_out / idx_out stably sorted by the low end_bit bits of
+// the key, and the segment table of the equal-key runs (KEY_NONE keys sort
+// last and belong to no segment)
+hipError_t tok_sort_segments(TokWork& w, uint32_t n, unsigned end_bit, hipStream_t s) {
+    const unsigned T = 256;
+    hipError_t e = rocprim::radix_sort_pairs(w.sort64_tmp, w.sort64_bytes, w.key_in, w.key_out, w.idx_in, w.idx_out,
+                                             n, 0u, end_bit, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_tok_heads, dim3(tblocks(n, T)), dim3(T), 0, s, w.key_out, n, w.head);
+    e = rocprim::exclusive_scan(w.scan_tmp, w.scan_bytes, w.head, w.head_scan, 0u, (size_t)n,
+                                rocprim::plus<uint32_t>(), s);
+    if (e != hipSuccess) return e;
+    hipMemsetAsync(w.n_seg, 0, sizeof(uint32_t), s);
+    hipLaunchKernelGGL(k_tok_segments, dim3(tblocks(n, T)), dim3(T), 0, s, w.key_out, w.head, w.head_scan, n,
+                       w.seg_start, w.n_seg);
+    return hipGetLastError();
+}
+
 hipError_t tok_launch(const TokState& ts, TokWork& w, const TokBatch& b, const TokOut& out, hipStream_t s) {
     const uint32_t n = b.n;
     if (!n) return hipSuccess;
@@ -488,16 +454,8 @@ hipError_t tok_launch(const TokState& ts, TokWork& w, const TokBatch& b, const T
         hipLaunchKernelGGL(k_ns_limit, dim3(ts.n_ns), dim3(64), 0, s, ts, b, w, out, nlo, nhi);
     }
     hipLaunchKernelGGL(k_tok_keys, dim3(tblocks(n, T)), dim3(T), 0, s, ts, b, w, out);
-    hipError_t e = rocprim::radix_sort_pairs(w.sort64_tmp, w.sort64_bytes, w.key_in, w.key_out, w.idx_in, w.idx_out,
-                                             n, 0u, 64u, s);
+    hipError_t e = tok_sort_segments(w, n, 64u, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_tok_heads, dim3(tblocks(n, T)), dim3(T), 0, s, w.key_out, n, w.head);
-    e = rocprim::exclusive_scan(w.scan_tmp, w.scan_bytes, w.head, w.head_scan, 0u, (size_t)n,
-                                rocprim::plus<uint32_t>(), s);
-    if (e != hipSuccess) return e;
-    hipMemsetAsync(w.n_seg, 0, sizeof(uint32_t), s);
-    hipLaunchKernelGGL(k_tok_segments, dim3(tblocks(n, T)), dim3(T), 0, s, w.key_out, w.head, w.head_scan, n,
-                       w.seg_start, w.n_seg);
     hipLaunchKernelGGL(k_tok_decide, dim3(tblocks(n, TD_T)), dim3(TD_T), 0, s, ts, b, w, out);
     return hipGetLastError();
 }

@@ -10,6 +10,7 @@
 #include "sf_concur.h"
 #include "sf_degrade.h"
 #include "sf_mem.h"
+#include "sf_rls.h"
 #include "sf_token.h"
 
 namespace sf {
@@ -52,6 +53,25 @@ inline int tok_work_ensure(TokWorkSet& s, uint32_t n, uint32_t max_batch, TokTem
         SF_TRY(m.alloc(&w.sort64_tmp, min16(w.sort64_bytes)));
         SF_TRY(m.alloc(&w.scan_tmp, min16(w.scan_bytes)));
         s.cap = (uint32_t)N;
+        return 0;
+    });
+}
+
+// RlsWork (sf_rls.h) beside the TokWork it is used with: room for n requests and n descriptors
+using RlsWorkSet = WorkSet<RlsWork>;
+
+inline int rls_work_ensure(RlsWorkSet& s, uint32_t n, uint32_t max_batch) {
+    if (n <= s.w.cap) return 0;
+    s.reset();
+    const size_t N = std::max(n, max_batch);
+    RlsWork& w = s.w;
+    DevPool& m = s.pool;
+    return s.grow([&]() -> int {
+        SF_TRY(m.alloc(&w.dom, min16(N * sizeof(RlsKey)))); SF_TRY(m.alloc(&w.req_err, min16(N)));
+        SF_TRY(m.alloc(&w.d_req, min16(N * 4))); SF_TRY(m.alloc(&w.d_fid, min16(N * 8)));
+        SF_TRY(m.alloc(&w.d_ts, min16(N * 8))); SF_TRY(m.alloc(&w.d_cnt, min16(N * 4)));
+        SF_TRY(m.alloc(&w.ctr, sizeof(RlsCounters)));
+        w.cap = (uint32_t)N;
         return 0;
     });
 }

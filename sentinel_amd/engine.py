@@ -86,6 +86,10 @@ def _declare(L):
     f("sf_serve_frames", I, P, C.POINTER(abi.sf_wire_batch), C.POINTER(abi.sf_wire_out))
     f("sf_string_key", C.c_uint64, C.c_char_p, C.c_uint32)
     f("sf_cluster_sum", I, P, C.c_int64, I, C.c_int64, C.POINTER(C.c_int64))
+    if hasattr(L, "sf_request_rls"):       # (absent from an older tree's library, as the authority calls below)
+        f("sf_request_rls", I, P, C.POINTER(abi.sf_rls_batch), C.POINTER(abi.sf_rls_results))
+        f("sf_rls_get_stats", I, P, C.POINTER(abi.sf_rls_stats))
+        f("sf_rls_flow_id", C.c_int64, C.c_char_p, U32)
     f("sf_comm_unique_id", I, C.c_char_p, C.c_size_t)
     f("sf_comm_init", I, P, I, I, C.c_char_p, C.c_size_t)
     f("sf_entry_node_allreduce", I, P, C.POINTER(abi.sf_node_state))
@@ -164,6 +168,16 @@ def token_shard(flow, param, namespaces, shard_count: int, batch: abi.HostTokenB
                                 abi.rules_array(abi.sf_namespace, list(namespaces)), len(namespaces), shard_count,
                                 batch.flow_id.ctypes.data, batch.flags.ctypes.data, batch.n, out.ctypes.data))
     return out
+
+
+def rls_flow_id(key) -> int:
+    """EnvoySentinelRuleConverter.generateFlowId of a key (str, or UTF-8 bytes):
+    -1 for a blank key; ValueError for ill-formed UTF-8."""
+    raw = key.encode("utf-8", "surrogatepass") if isinstance(key, str) else bytes(key)
+    v = lib().sf_rls_flow_id(raw, len(raw))
+    if v == -(1 << 63):
+        raise ValueError("ill-formed UTF-8")
+    return v
 
 
 def comm_unique_id() -> bytes:
@@ -720,6 +734,39 @@ class FlowEngine:
         v = C.c_int64()
         _check(lib().sf_cluster_sum(self.h, flow_id, event, now, C.byref(v)))
         return v.value
+
+    # ---- Envoy rate-limit service (shouldRateLimit; batches from sentinel_amd.rls.pack_requests)
+    def request_rls(self, batch: abi.HostRlsBatch, device: bool = False) -> abi.HostRlsResults:
+        """device=True: the batch and the results live in device memory for the call."""
+        out = abi.HostRlsResults(batch.n, batch.n_desc)
+        if not device:
+            b, r = batch.c_struct(), out.c_struct()
+            _check(lib().sf_request_rls(self.h, C.byref(b), C.byref(r)))
+            return out
+        bufs = {}
+        try:
+            for name in batch.ARRAYS:
+                if getattr(batch, name) is not None:
+                    bufs[name] = DeviceArray(self, getattr(batch, name))
+            res = {name: DeviceArray.empty(self, getattr(out, name).shape, dt) for name, dt in out.FIELDS}
+            bufs.update(("out_" + k, v) for k, v in res.items())
+            b = batch.c_struct({k: v.ptr for k, v in bufs.items()})
+            r = abi.sf_rls_results()
+            r.mem = abi.MEM_DEVICE
+            for name, _ in out.FIELDS:
+                setattr(r, name, res[name].ptr)
+            _check(lib().sf_request_rls(self.h, C.byref(b), C.byref(r)))
+            for name, _ in out.FIELDS:
+                setattr(out, name, res[name].numpy())
+        finally:
+            for v in bufs.values():
+                v.free()
+        return out
+
+    def rls_stats(self) -> abi.sf_rls_stats:
+        s = abi.sf_rls_stats()
+        _check(lib().sf_rls_get_stats(self.h, C.byref(s)))
+        return s
 
     def sync(self):
         _check(lib().sf_sync(self.h))
