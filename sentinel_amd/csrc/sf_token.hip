@@ -193,8 +193,9 @@ __global__ void k_tok_keys(TokState ts, TokBatch b, TokWork w, TokOut out) {
                 if (ts.items[rule.item_off + k].tag == SF_TAG_NULL) { raw = ts.items[rule.item_off + k].count; break; }
             const double thr = rule.threshold_type == SF_THRESHOLD_GLOBAL ? raw : raw * connected;
             const double next = thr - 0.0 - b.count[i];
-            out.status[i] = next >= 0 ? SF_TOKEN_OK : SF_TOKEN_BLOCKED;
-            out.remaining[i] = next >= 0 ? j_d2i(next) : 0;
+            const bool pass = !(next < 0);                       // :66 blocks on nextRemaining < 0: a NaN passes
+            out.status[i] = pass ? SF_TOKEN_OK : SF_TOKEN_BLOCKED;
+            out.remaining[i] = pass ? j_d2i(next) : 0;
             out.wait[i] = 0;
         } else {
             const uint64_t hi = ((uint64_t)(r + 1) << 32) | b.ptag[v0];
@@ -370,7 +371,7 @@ __global__ void __launch_bounds__(TD_T) k_tok_decide(TokState ts, TokBatch b, To
         const int64_t t = b.ts[i];
         const int32_t c = b.count[i];
         const double next = thr - (double)cp_sum(slot, S, wl, I, t) / isec - c;   // getSum(value)
-        if (next >= 0) {
+        if (!(next < 0)) {                                       // :66 nextRemaining < 0 blocks (a NaN count passes)
             cp_add(slot, S, wl, t, c);                           // addValue :72-84
             out.status[i] = SF_TOKEN_OK; out.remaining[i] = j_d2i(next);
         } else {
