@@ -431,7 +431,7 @@ typedef struct sf_stats {         /* device-clock timings, summed over sf_submit
      * settled by the exact solve, chunks on the serial path, solve rounds,
      * events the serial part walked */
     uint64_t xw_chunks_exact, xw_chunks_serial, xw_rounds, xw_serial_events;
-    uint64_t sys_exchanges;       /* all-gathers of sf_submit_node's per-window exchange (SF_SYSX_MSG_BYTES each, plan step) */
+    uint64_t sys_exchanges;       /* all-gathers of sf_submit_node's per-window exchange (SF_SYSX_MSG_BYTES or SF_SYSX_WIDE_MSG_BYTES each, plan step) */
 } sf_stats;
 
 typedef struct sf_heavy_profile { /* diagnostics: one heavy segment of the last sf_submit */
@@ -885,17 +885,20 @@ int  sf_format_metric_rows(sf_engine* e, const sf_metric_row* rows, uint32_t n, 
  * events of the same node batch, in submission order, and `seq` = their
  * global sequence numbers (increasing; time non-decreasing in them).  The
  * ranks exchange per-window aggregates only (a rank's ENTRY_NODE contribution
- * and a 128-bin histogram of its undecided IN entries per level, 4.2 KB): with
+ * and a 128-bin histogram of its undecided IN entries per level, 4.2 KB; for a
+ * SystemRule with a thread, average-RT or firing load (BBR) check the wide
+ * format, 64 bins of the exit- and entry-side sums every check reads, 10.1 KB): with
  * `allgather` NULL over the engine's RCCL communicator (sf_comm_init; device
  * buffers, stream-ordered), else through the callback, which must return
  * rank 0's `bytes`, rank 1's, ... in `recv` (0 = success; host buffers).  The
  * verdicts, and every rank's ENTRY_NODE, equal one engine deciding the whole
- * node batch.  SF_ERR_UNSUPPORTED (every rank alike) when a loaded SystemRule
- * has thread / average-RT / BBR checks or an IN entry has acquireCount < 0:
- * use the event all-gather protocol (sf_system_plan, sf_submit_forced,
- * sf_entry_node_add).  Without SystemRules it is sf_submit. */
+ * node batch.  SF_ERR_UNSUPPORTED (every rank alike) when an IN entry of the
+ * node batch has acquireCount < 0: use the event all-gather protocol
+ * (sf_system_plan, sf_submit_forced, sf_entry_node_add).  Without SystemRules
+ * it is sf_submit. */
 typedef int (*sf_allgather_fn)(void* ctx, const void* send, void* recv, uint64_t bytes);
 #define SF_SYSX_MSG_BYTES 4224     /* one rank's message of a plan level (sf_sysx.h SX_WORDS * 8) */
+#define SF_SYSX_WIDE_MSG_BYTES 10368   /* the same for thread / RT / BBR rules (sf_sysx.h SXW_WORDS * 8) */
 int  sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, sf_verdicts* out,
                     sf_allgather_fn allgather, void* ctx);
 

@@ -31,6 +31,8 @@ SF_WS_ABSENT = -(2 ** 63)
 RES_ENTRY_NODE = 0xFFFFFFFF      # sf_metric_row.resource of Constants.ENTRY_NODE
 SF_MAX_RULES_PER_RESOURCE = 8
 SF_MAX_ARGS = 4
+# sf_submit_node: one rank's message of a plan level (QPS / CPU rules; thread / RT / BBR rules)
+SYSX_MSG_BYTES, SYSX_WIDE_MSG_BYTES = 4224, 10368
 
 TAG_NULL, TAG_INT, TAG_LONG, TAG_STRING, TAG_DOUBLE, TAG_BOOL, TAG_OTHER, TAG_BYTE, TAG_SHORT, TAG_FLOAT = range(10)
 TAG_COLLECTION = 0x40        # a Collection / array argument: elements listed in the CSR

@@ -218,6 +218,9 @@ struct sf_engine {
     int64_t* sx_seq = nullptr;            // [max_batch] device copy of host sequence numbers
     uint8_t* sx_ibuf = nullptr;           // [max_batch] inert flags of the round
     std::vector<int64_t> sx_hsend, sx_hrecv;   // host side of a callback all-gather
+    int64_t* sxw_msg = nullptr;           // the wide kinds: this rank's message [SXW_WORDS]
+    SxwSeg* sxw_segs = nullptr;           // [SXW_MAX_SEGS] device copy of a round's settled runs
+    std::vector<SxwSeg> sxw_hsegs;
     int64_t* agg = nullptr;               // [ws (S+60) | gws (S+60) | vals ((S+60)*6+1) | minrt (S+60)]
     // DegradeSlot circuit breakers (sf_degrade.hip)
     DegradeDev dg{};
@@ -1834,17 +1837,21 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
     SF_TRY(check_event_batch(e, in));
     std::lock_guard<std::mutex> lk(e->mu);
     if (!e->sys.check) return in->n ? submit_core(e, in, out, false) : SF_OK;   // nothing node-wide to decide
-    if (!sx_rule_ok(e->sys))
-        return fail(SF_ERR_UNSUPPORTED, "SystemRule with thread / RT / BBR checks: the event all-gather protocol "
-                                        "(sf_system_plan + sf_submit_forced + sf_entry_node_add)");
+    // thread / average-RT / BBR checks: the wide message format and plan step (sf_sysx.h)
+    const bool wide = !sx_rule_ok(e->sys);
     if (!allgather && !e->comm) return fail(SF_ERR_INVALID, "no exchange: sf_comm_init or an all-gather callback");
     SF_TRY(drain(e));
     const uint32_t n = in->n, N = e->cfg.shard_count;
     hipStream_t s = e->stream;
     if (!e->sx_msg) SF_TRY(e->pool.alloc(&e->sx_msg, SX_WORDS * 8));
+    if (wide && !e->sxw_msg) SF_TRY(e->pool.alloc(&e->sxw_msg, SXW_WORDS * 8));
+    if (wide && !e->sxw_segs) SF_TRY(e->pool.alloc(&e->sxw_segs, (size_t)SXW_MAX_SEGS * sizeof(SxwSeg)));
+    if (wide) e->sxw_hsegs.resize(SXW_MAX_SEGS);
+    const size_t mwords = wide ? SXW_WORDS : SX_WORDS;
+    int64_t* const msg = wide ? e->sxw_msg : e->sx_msg;    // the level messages (the header uses sx_msg)
     if (!e->sx_ibuf) SF_TRY(e->pool.alloc(&e->sx_ibuf, e->cfg.max_batch));
     SF_TRY(sys_buffers_ensure(e));
-    SF_TRY(sx_recv_reserve(e, (size_t)N * SX_WORDS));
+    SF_TRY(sx_recv_reserve(e, (size_t)N * mwords));
     const bool with_ox = in->origin || e->st.xmap;
     SF_TRY(reserve_for_batch(e, in, with_ox, in->n));
     Slot& sl = e->slot[e->cur];
@@ -1864,7 +1871,7 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
     DevState stl = e->st;
     stl.err = w.err;
     SxArgs a{};
-    a.b = b; a.seq = dseq; a.msg = e->sx_msg;
+    a.b = b; a.seq = dseq; a.msg = e->sx_msg; a.vstatus = dv.status;
     a.r = e->sys; a.S = stl.S; a.wl = stl.wl; a.interval = stl.interval; a.max_rt = stl.max_rt;
     a.interval_sec = stl.interval / 1000.0; a.st = stl;
     a.ibuf = e->st.n_prule ? e->sx_ibuf : nullptr;
@@ -1921,39 +1928,59 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
     HIP_TRY(hipStreamSynchronize(s));
     uint32_t* d_lq = (uint32_t*)e->sx_recv.p;     // (sx_locate's result: the recv buffer is free then)
     // ---- rounds
-    HIP_TRY(sx_nodelta(e->sx_msg, s));
+    a.msg = msg;
+    HIP_TRY(wide ? sxw_nodelta(msg, s) : sx_nodelta(msg, s));
     int64_t sp = wseq.empty() ? INT64_MAX : wseq[0];
     uint32_t lp = 0, rounds = 0;
     size_t j = 0;
     uint64_t levels = 0;
+    // The wide kinds: how many sequence numbers past s_p a round plans.  Where a
+    // thread or RT rule hovers at its threshold a round ends at an unknown entry
+    // a few thousand events on, and binning the whole rest of the window first
+    // costs a level per round; a range of 64^k numbers needs k levels.  Set from
+    // the plan's own results (q), so it is the same on every rank: twice the
+    // last round's length, rounded up to 64^k (k >= 2); 64 times wider after a
+    // round that settled its whole range; no limit after a window's end.
+    int64_t wcap = INT64_MAX;
     for (;;) {
         const bool fin = wseq.empty() || sp >= seq_end;
         while (!fin && j + 1 < wseq.size() && wseq[j + 1] <= sp) j++;
-        const int64_t lo = fin ? 0 : sp, hi = fin ? 0 : (j + 1 < wseq.size() ? wseq[j + 1] : seq_end);
+        const int64_t lo = fin ? 0 : sp, hi_w = fin ? 0 : (j + 1 < wseq.size() ? wseq[j + 1] : seq_end);
+        const int64_t hi = (wide && !fin && hi_w - lo > wcap) ? lo + wcap : hi_w;
         const int64_t wstart = fin ? 0 : (C0 + wkey[j]) * a.g;
         SxPlan hp;
+        SxwPlan hw;
         sx_begin(&hp, lo, hi);
+        sxw_begin(&hw, lo, hi);
         for (int level = 0;; level++) {
-            const hipError_t le = sx_stats(a, hp, lp, level == 0, s);
+            const hipError_t le = wide ? sxw_stats(a, hw, lp, level == 0, s) : sx_stats(a, hp, lp, level == 0, s);
             if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("exchange stats: ") + hipGetErrorString(le));
-            SF_TRY(gather(e->sx_msg, SX_WORDS, h));
+            SF_TRY(gather(msg, mwords, h));
             levels++;
             if (level == 0) {
                 // the node's ENTRY_NODE contribution of the last sub-batch (its plan window is the key)
                 int64_t key = -1;
-                for (uint32_t k = 0; k < N; k++) key = std::max(key, h[(size_t)k * SX_WORDS + SXD_KEY]);
+                for (uint32_t k = 0; k < N; k++) key = std::max(key, h[(size_t)k * mwords + SXD_KEY]);
                 if (key >= 0) {
                     const int64_t W = (C0 + key) * a.g;
-                    sx_apply_delta(h.data(), (int)N, &enh, W - W % a.wl, a.S, a.wl, W - W % 1000, a.max_rt);
+                    sx_apply_delta(h.data(), (int)N, &enh, W - W % a.wl, a.S, a.wl, W - W % 1000, a.max_rt, mwords);
                 }
-                hp.P = sys_base(enh.second, a.S, a.wl, a.interval, a.max_rt, enh.threads, wstart).P;
+                hw.base = sys_base(enh.second, a.S, a.wl, a.interval, a.max_rt, enh.threads, wstart);
+                hp.P = hw.base.P;
             }
-            sx_reduce(h.data(), (int)N, &hp, a.r, a.interval_sec);
+            if (wide) {
+                sxw_reduce(h.data(), (int)N, &hw, e->sxw_hsegs.data(), a.r, a.S, a.interval_sec);
+                hp.q = hw.q; hp.done = hw.done;
+            } else {
+                sx_reduce(h.data(), (int)N, &hp, a.r, a.interval_sec);
+            }
             if (hp.done) break;
-            if (level > 64) return fail(SF_ERR_DEVICE, "exchange plan did not converge");
+            if (level > SXW_MAX_LEVELS) return fail(SF_ERR_DEVICE, "exchange plan did not converge");
         }
         if (fin) break;
+        // (the plan is the same on every rank, so these fail on all of them together)
         if (hp.q <= sp || hp.q > hi) return fail(SF_ERR_DEVICE, "exchange plan made no progress");
+        if (wide && hw.overflow) return fail(SF_ERR_DEVICE, "exchange plan: too many settled runs");
         uint32_t lq;
         if (in->mem == SF_MEM_HOST) {
             lq = (uint32_t)(std::lower_bound(seq + lp, seq + n, hp.q) - seq);
@@ -1964,15 +1991,30 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
         }
         if (lq < lp || lq > n) return fail(SF_ERR_DEVICE, "exchange plan: bad local range");
         if (lq > lp) {
-            hipError_t le = sx_mask(a, e->sys_mask, lp, lq, hp.P, s);
+            if (wide && hw.nseg)
+                HIP_TRY(hipMemcpyAsync(e->sxw_segs, e->sxw_hsegs.data(), (size_t)hw.nseg * sizeof(SxwSeg),
+                                       hipMemcpyHostToDevice, s));
+            hipError_t le = wide ? sxw_mask(a, e->sys_mask, lp, lq, e->sxw_segs, hw.nseg, s)
+                                 : sx_mask(a, e->sys_mask, lp, lq, hp.P, s);
             if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("exchange mask: ") + hipGetErrorString(le));
             DevBatch v;
             DevVerdicts dvv;
             SF_TRY(decide_view(e, sl, stl, b, dv, lp, lq, with_ox, v, dvv));
-            le = launch_entry_delta(stl, v, dvv.status, e->en_acc, e->sx_msg, wkey[j], s);
+            le = launch_entry_delta(stl, v, dvv.status, e->en_acc, msg, wkey[j], s);
             if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("exchange delta: ") + hipGetErrorString(le));
         } else {
-            HIP_TRY(sx_nodelta(e->sx_msg, s));
+            HIP_TRY(wide ? sxw_nodelta(msg, s) : sx_nodelta(msg, s));
+        }
+        if (wide) {
+            if (hp.q < hi) {
+                const int64_t len = hp.q - sp;
+                wcap = (int64_t)SXW_B * SXW_B;
+                while (wcap < 2 * len && wcap < ((int64_t)1 << 48)) wcap *= SXW_B;
+            } else if (hi < hi_w) {
+                wcap = wcap < ((int64_t)1 << 48) ? wcap * SXW_B : INT64_MAX;
+            } else {
+                wcap = INT64_MAX;
+            }
         }
         lp = lq;
         sp = hp.q;

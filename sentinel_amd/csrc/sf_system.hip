@@ -466,4 +466,136 @@ hipError_t sx_mask(const SxArgs& a, uint8_t* mask, uint32_t lp, uint32_t lq, int
     return hipGetLastError();
 }
 
+// ---- the wide kinds (sf_sysx.h): thread / average-RT / BBR rules
+__global__ void k_sxw_clear(int64_t* msg, bool keep_delta) {
+    const int i = threadIdx.x + blockIdx.x * blockDim.x;
+    if (i < SX_DELTA) { if (!keep_delta) msg[i] = i == SXD_KEY ? -1 : 0; }
+    else if (i < SXW_WORDS) msg[i] = sxw_identity((i - SX_DELTA) / SXW_B);
+}
+hipError_t sxw_nodelta(int64_t* msg, hipStream_t s) {
+    hipLaunchKernelGGL(k_sxw_clear, dim3((SXW_WORDS + 255) / 256), dim3(256), 0, s, msg, false);
+    return hipGetLastError();
+}
+
+// word (f, bin) of a bin table (LDS or the message) += / min= / max= v: plain
+// integer atomics, so the table does not depend on their order
+__device__ __forceinline__ void sxw_put(int64_t* tab, int f, int64_t bin, int64_t v) {
+    int64_t* p = tab + (size_t)f * SXW_B + bin;
+    if (f == SXW_XC_MIN || f == SXW_XU_MIN || f == SXW_CMIN) atomicMin((long long*)p, (long long)v);
+    else if (f == SXW_CMAX) atomicMax((long long*)p, (long long)v);
+    else atomicAdd((unsigned long long*)p, (unsigned long long)v);
+}
+
+// One pass over this rank's events of the level's range.  One thread per
+// contiguous run of events (sequence numbers increase, so a run's bin changes
+// rarely): the SXW_F sums in registers, one set of LDS atomics per (run, bin),
+// then the workgroup's non-empty words into the message.
+__global__ void __launch_bounds__(SX_T) k_sxw_stats(SxArgs a, uint32_t lp, bool level0, int64_t lo, int64_t hi,
+                                                    int64_t w) {
+    __shared__ uint32_t rng[2];
+    __shared__ int64_t tab[SXW_F * SXW_B];
+    if (threadIdx.x == 0) {
+        rng[0] = sx_lower(a.seq, lp, a.b.n, lo);
+        rng[1] = sx_lower(a.seq, rng[0], a.b.n, hi);
+    }
+    for (int k = threadIdx.x; k < SXW_F * SXW_B; k += SX_T) tab[k] = sxw_identity(k / SXW_B);
+    __syncthreads();
+    const uint32_t i0 = rng[0], i1 = rng[1];
+    const uint64_t nth = (uint64_t)gridDim.x * SX_T, len = i1 - i0;
+    const uint32_t per = (uint32_t)((len + nth - 1) / nth);
+    const uint64_t t = (uint64_t)blockIdx.x * SX_T + threadIdx.x;
+    const uint64_t r0 = (uint64_t)i0 + t * per;
+    const uint32_t r1 = (uint32_t)std::min<uint64_t>(r0 + per, i1);
+    int64_t v[SXW_F];
+    int64_t bin = -1;
+    auto reset = [&]() {
+#pragma unroll
+        for (int f = 0; f < SXW_F; f++) v[f] = sxw_identity(f);
+    };
+    auto flush = [&]() {
+        if (bin < 0 || bin >= SXW_B) return;
+#pragma unroll
+        for (int f = 0; f < SXW_F; f++)
+            if (v[f] != sxw_identity(f)) sxw_put(tab, f, bin, v[f]);
+    };
+    reset();
+    const int64_t M = a.r.max_rt;
+    for (uint64_t i = r0; i < r1; i++) {
+        const uint8_t f = a.b.flags[i];
+        if (!(f & SF_EV_IN)) continue;
+        const bool is_exit = (f & SF_EV_EXIT) != 0;
+        if (!is_exit && (f & SF_EV_BLOCKED)) continue;           // blocked before SystemSlot: no system verdict
+        const int64_t k = (a.seq[i] - lo) / w;
+        if (k != bin) { flush(); reset(); bin = k; }
+        const int32_t c = a.b.cnt[i];
+        if (!is_exit) {
+            bool inert;
+            if (level0) {
+                inert = a.ibuf && param_inert(a.st, a.b, (uint32_t)i, c, a.b.ts[i]);
+                if (a.ibuf) a.ibuf[i] = inert ? 1 : 0;
+            } else {
+                inert = a.ibuf && a.ibuf[i];
+            }
+            v[SXW_NE]++;
+            if (!inert) { v[SXW_NB]++; v[SXW_NB_C] = wadd(v[SXW_NB_C], c > 0 ? c : 0); }
+            if (c < v[SXW_CMIN]) v[SXW_CMIN] = c;
+            if (c > v[SXW_CMAX]) v[SXW_CMAX] = c;
+            continue;
+        }
+        const SysExitQ q = sys_exit_q(a.b.ts, a.b.cnt, a.b.flags, a.b.eref, a.b.cts, a.vstatus, lp, (uint32_t)i, M);
+        if (q.xc) {
+            v[SXW_XC]++; v[SXW_XC_C] = wadd(v[SXW_XC_C], q.xc_c); v[SXW_XC_RT] = wadd(v[SXW_XC_RT], q.xc_rt);
+            if (q.xc_min < v[SXW_XC_MIN]) v[SXW_XC_MIN] = q.xc_min;
+            bool bad = q.xc_c <= 0 || q.xc_rt < 0;
+            if (M != INT64_MAX) {
+                const __int128 d = (__int128)q.xc_rt - (__int128)M * q.xc_c;
+                const __int128 lim = (__int128)1 << 62;
+                if (d >= lim || d <= -lim) bad = true;
+                else if (d > 0) { v[SXW_RP_LO] += (int64_t)d & 0xFFFFFFFFll; v[SXW_RP_HI] += (int64_t)d >> 32; }
+                else { v[SXW_RN_LO] += (int64_t)(-d) & 0xFFFFFFFFll; v[SXW_RN_HI] += (int64_t)(-d) >> 32; }
+            }
+            if (bad) v[SXW_XBAD]++;
+        } else if (q.xu) {
+            v[SXW_XU]++; v[SXW_XU_C] = wadd(v[SXW_XU_C], q.xu_c); v[SXW_XU_BAD] += q.xu_bad;
+            if (q.xu_min < v[SXW_XU_MIN]) v[SXW_XU_MIN] = q.xu_min;
+            v[SXW_XUP_LO] += q.xu_pos & 0xFFFFFFFFll; v[SXW_XUP_HI] += q.xu_pos >> 32;
+        }
+    }
+    flush();
+    __syncthreads();
+    for (int k = threadIdx.x; k < SXW_F * SXW_B; k += SX_T) {
+        const int f = k / SXW_B;
+        const int64_t x = tab[k];
+        if (x != sxw_identity(f)) sxw_put(a.msg + SX_DELTA, f, k - f * SXW_B, x);
+    }
+}
+hipError_t sxw_stats(const SxArgs& a, const SxwPlan& pl, uint32_t lp, bool level0, hipStream_t s) {
+    hipLaunchKernelGGL(k_sxw_clear, dim3((SXW_WORDS + 255) / 256), dim3(256), 0, s, a.msg, level0);
+    if (pl.done) return hipGetLastError();
+    const uint64_t rest = a.b.n > lp ? a.b.n - lp : 0;
+    const uint32_t nb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1024, (rest + 16 * SX_T - 1) / (16 * SX_T)));
+    hipLaunchKernelGGL(k_sxw_stats, dim3(nb), dim3(SX_T), 0, s, a, lp, level0, pl.lo, pl.hi, pl.w);
+    return hipGetLastError();
+}
+
+// the outcome of the settled run that holds the entry's sequence number
+__global__ void k_sxw_mask(SxArgs a, uint8_t* mask, uint32_t lp, uint32_t lq, const SxwSeg* segs, int nseg) {
+    const uint32_t i = lp + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= lq) return;
+    uint8_t m = SYS_NONE;
+    if (sx_in_entry(a.b, i)) {
+        const int64_t sq = a.seq[i];
+        int lo = 0, hi = nseg;                                   // first run with lo > sq
+        while (lo < hi) { const int mid = lo + (hi - lo) / 2; if (segs[mid].lo > sq) hi = mid; else lo = mid + 1; }
+        if (lo > 0 && sq < segs[lo - 1].hi) m = (uint8_t)segs[lo - 1].outcome;
+        else *a.st.err = SF_ERR_INVALID;                         // (cannot happen: every entry before q is settled)
+    }
+    mask[i] = m;
+}
+hipError_t sxw_mask(const SxArgs& a, uint8_t* mask, uint32_t lp, uint32_t lq, const SxwSeg* segs, int nseg,
+                    hipStream_t s) {
+    if (lq > lp) hipLaunchKernelGGL(k_sxw_mask, dim3((lq - lp + 255) / 256), dim3(256), 0, s, a, mask, lp, lq, segs, nseg);
+    return hipGetLastError();
+}
+
 }  // namespace sf

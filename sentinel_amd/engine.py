@@ -466,9 +466,12 @@ class FlowEngine:
         semantics, by the per-window exchange (sf_sysx.h).  ``comm``: an object
         with ``allgather_bytes(np.uint8 array) -> [rank 0's bytes, rank 1's,
         ...]`` (e.g. system_shard.TorchComm over gloo), or None for the
-        engine's RCCL communicator (sf_comm_init).  Raises EngineError with
-        code SF_ERR_UNSUPPORTED on every rank alike when the SystemRules need
-        the event all-gather protocol."""
+        engine's RCCL communicator (sf_comm_init).  Inbound-QPS and CPU rules
+        exchange abi.SYSX_MSG_BYTES per rank and plan level, rules with a
+        thread, average-RT or firing load (BBR) check abi.SYSX_WIDE_MSG_BYTES.
+        Raises EngineError with code SF_ERR_UNSUPPORTED on every rank alike
+        when an IN entry of the node batch has acquireCount < 0: that batch
+        needs the event all-gather protocol."""
         out = abi.HostVerdicts(batch.n)
         b, v = batch.c_struct(), out.c_struct()
         sq = np.ascontiguousarray(seq, np.int64)

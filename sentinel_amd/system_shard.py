@@ -2,10 +2,11 @@
 
 Two protocols.  ``submit_node`` uses the engine's per-window exchange
 (sf_submit_node, sentinel_amd/csrc/sf_sysx.h): the ranks all-gather per-window
-aggregates (each rank's ENTRY_NODE contribution and a 128-bin histogram of its
-undecided IN entries, 4.2 KB per rank and level) over RCCL or the ``comm``
-callback, for SystemRules that read only the inbound-QPS (and CPU) check.
-Every other SystemRule (thread, average RT, BBR) and batches with a negative
+aggregates over RCCL or the ``comm`` callback: each rank's ENTRY_NODE
+contribution and a 128-bin histogram of its undecided IN entries (4.2 KB per
+rank and level) for SystemRules that read only the inbound-QPS (and CPU)
+check, or 64 bins of the exit- and entry-side sums every check reads (10.1 KB)
+for thread, average-RT and BBR rules.  Only batches with a negative
 acquireCount fall back to ``submit_node_gather``, the event all-gather round
 protocol below.
 
@@ -142,7 +143,8 @@ def submit_node(eng, batch: abi.HostBatch, seq: np.ndarray, comm=None) -> abi.Ho
     """This rank's ``batch`` (its shard's events in submission order, ``seq``
     their increasing sequence numbers in the node's stream) with the node-wide
     SystemRule semantics: the engine's per-window exchange when the engine has
-    one and its rules allow it, else the event all-gather protocol.  ``comm``
+    one, else (or for a batch it refuses, SF_ERR_UNSUPPORTED: a negative
+    acquireCount) the event all-gather protocol.  ``comm``
     None: a TorchComm over the default process group."""
     comm = comm or TorchComm()
     if hasattr(eng, "submit_node"):
