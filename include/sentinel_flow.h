@@ -957,7 +957,7 @@ typedef struct sf_degrade_rule {   /* DegradeRule (DegradeRule.java) */
     uint32_t resource;
     int32_t  grade;                /* SF_DEGRADE_GRADE_* */
     double   count;                /* RT: max allowed rt (Math.round); ratio / count threshold */
-    int32_t  time_window_s;        /* recovery timeout = time_window_s * 1000 */
+    int32_t  time_window_s;        /* recovery timeout = time_window_s * 1000 (Java int arithmetic, wraps) */
     int32_t  min_request_amount;   /* default 5 */
     double   slow_ratio_threshold; /* RT grade only, default 1.0 */
     int32_t  stat_interval_ms;     /* default 1000 */

@@ -67,7 +67,8 @@ class Breaker:
         self.max_rt = java_round(r["count"])             # ResponseTimeCircuitBreaker :52
         self.threshold = float(r["slow_ratio_threshold"] if self.grade == GRADE_RT else r["count"])
         self.min_req = int(r["min_request_amount"])
-        self.recovery = int(r["time_window_s"]) * 1000   # AbstractCircuitBreaker :54
+        # int recoveryTimeoutMs = timeWindow * 1000: Java int arithmetic, wraps (AbstractCircuitBreaker :36,54)
+        self.recovery = ((int(r["time_window_s"]) * 1000 + (1 << 31)) & 0xFFFFFFFF) - (1 << 31)
         self.interval = int(r["stat_interval_ms"])
         self.state = CLOSED
         self.next_retry = 0
@@ -138,7 +139,16 @@ class Breaker:
 
 
 class DegradeOracle:
-    def __init__(self):
+    def __init__(self, log=False):
+        """log: record every state transition and window roll of submit() in
+        ``self.transitions`` as (event, breaker, from_state, to_state, rolled):
+        ``event`` counts the events submitted so far (batches concatenated),
+        ``rolled`` says the event created or reset the breaker's bucket.  A
+        probe that a later breaker refused (HALF_OPEN and back) is recorded
+        as (event, breaker, OPEN, OPEN, False).  Off by default; recording
+        changes no decision."""
+        self.transitions = [] if log else None
+        self.n_seen = 0
         self.breakers = []        # load order of valid rules
         self.by_res = {}          # resource -> [breaker indices] in rule order
         self.created = {}         # entries passed in earlier batches are looked up by create_ts
@@ -167,9 +177,13 @@ class DegradeOracle:
         n = len(res)
         status = np.zeros(n, np.uint8)
         rule_idx = np.zeros(n, np.uint16)
+        log, base = self.transitions, self.n_seen
+        self.n_seen += n
         for i in range(n):
             r, t, f = int(res[i]), int(ts[i]), int(flags[i])
             cbs = self.by_res.get(r, ())
+            if log is not None:
+                before = [(self.breakers[b].state, self.breakers[b].ws) for b in cbs]
             if not f & EV_EXIT:
                 if f & EV_BLOCKED:                          # blocked by an earlier slot: DegradeSlot never runs
                     status[i] = V_BLOCK_OTHER
@@ -187,9 +201,13 @@ class DegradeOracle:
                     for b in moved:                         # whenTerminate hook (:113-129)
                         if self.breakers[b].state == HALF_OPEN:
                             self.breakers[b].state = OPEN
+                            if log is not None:             # a probe sent back: OPEN -> OPEN, no roll
+                                log.append((base + i, b, OPEN, OPEN, False))
                     status[i], rule_idx[i] = V_BLOCK_DEGRADE, blocked
                 else:
                     status[i] = V_PASS
+                    if log is not None:
+                        self._log(base + i, cbs, before)
                 continue
             ref = -1 if entry_ref is None else int(entry_ref[i])
             if ref == -2:                                   # entry blocked in an earlier batch
@@ -206,7 +224,15 @@ class DegradeOracle:
             for b in cbs:                                    # DegradeSlot.exit (:85-91)
                 self.breakers[b].on_complete(t, rt, f & EV_ERROR)
             status[i] = V_EXIT
+            if log is not None:
+                self._log(base + i, cbs, before)
         return status, rule_idx
+
+    def _log(self, ev, cbs, before):
+        for b, (st0, ws0) in zip(cbs, before):
+            cb = self.breakers[b]
+            if cb.state != st0 or cb.ws != ws0:
+                self.transitions.append((ev, b, st0, cb.state, cb.ws != ws0))
 
     def state(self, k):
         b = self.breakers[k]

@@ -1452,7 +1452,8 @@ int so_load_degrade_rules(so_engine* e, const sf_degrade_rule* rules, uint32_t n
             b->rule = *r;
             b->max_rt = so_java_round(r->count);
             b->threshold = r->grade == SF_DEGRADE_GRADE_RT ? r->slow_ratio_threshold : r->count;
-            b->recovery = (int64_t)r->time_window_s * 1000;
+            /* int recoveryTimeoutMs = timeWindow * 1000: Java int arithmetic, wraps */
+            b->recovery = (int64_t)(int32_t)((uint32_t)r->time_window_s * 1000u);
             b->state = SF_CB_CLOSED;
         }
         k++;

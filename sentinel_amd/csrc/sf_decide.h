@@ -1143,7 +1143,8 @@ inline DevBreakerRule make_dev_breaker_rule(const sf_degrade_rule& r) {
     d.min_req = r.min_request_amount;
     d.max_rt = j_round(r.count);                             // Math.round (ResponseTimeCircuitBreaker.java:52)
     d.thr = r.grade == SF_DEGRADE_GRADE_RT ? r.slow_ratio_threshold : r.count;
-    d.recovery = (int64_t)r.time_window_s * 1000;
+    // int recoveryTimeoutMs = timeWindow * 1000: Java int arithmetic, wraps (AbstractCircuitBreaker.java:36,54)
+    d.recovery = (int64_t)(int32_t)((uint32_t)r.time_window_s * 1000u);
     d.interval = r.stat_interval_ms;
     return d;
 }

@@ -12,7 +12,7 @@ struct DevBreakerRule {
     int32_t min_req;     // minRequestAmount
     int64_t max_rt;      // Math.round(count) (RT grade)
     double  thr;         // slowRatioThreshold (RT) or count (exception grades)
-    int64_t recovery;    // timeWindow * 1000
+    int64_t recovery;    // timeWindow * 1000 (Java int arithmetic, wraps)
     int64_t interval;    // statIntervalMs (LeapArray(1, interval))
 };
 

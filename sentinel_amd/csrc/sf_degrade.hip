@@ -411,8 +411,10 @@ hipError_t dg_launch(const DegradeDev& d, DegradeWork& w, const DegradeBatch& b,
                      int32_t* wait, hipStream_t s) {
     if (b.n == 0) return hipSuccess;
     k_dg_keys<<<blocks(b.n), BLK, 0, s>>>(d, b, w.keys_in, w.idx_in, status, rule, wait, w.err);
-    k_dg_clock<<<1, 1, 0, s>>>(b, w.err);
-    if (d.n_rres == 0) return hipGetLastError();
+    if (d.n_rres == 0) {
+        k_dg_clock<<<1, 1, 0, s>>>(b, w.err);
+        return hipGetLastError();
+    }
     size_t bytes = w.sort_tmp_bytes;
     hipError_t e = rocprim::radix_sort_pairs(w.sort_tmp, bytes, w.keys_in, w.keys_out, w.idx_in, w.idx_out, b.n, 0u,
                                              d.key_bits, s);
@@ -430,5 +432,7 @@ hipError_t dg_launch(const DegradeDev& d, DegradeWork& w, const DegradeBatch& b,
     k_dg_inv<<<blocks(b.n), BLK, 0, s>>>(b.n, w.keys_out, w.idx_out, d.n_rres, w.inv);
     k_dg_gather<<<blocks(b.n), BLK, 0, s>>>(b, w.keys_out, w.idx_out, d.n_rres, w.inv, w.sev);
     k_dg_wave<<<waves, 64, 0, s>>>(d, b, w.sev, w.beg, w.end, status, rule, w.err, w.heavy, w.n_heavy);
+    // after the walks: they are the ones that find a bad entry_ref
+    k_dg_clock<<<1, 1, 0, s>>>(b, w.err);
     return hipGetLastError();
 }
