@@ -1362,7 +1362,8 @@ __device__ void heavy_param(const DevState& st, const SegIO& io, const HeavyCtx&
             atomicOr(hc.passbits + (q >> 6), pm << sh);
             if (sh) atomicOr(hc.passbits + (q >> 6) + 1, pm >> (64 - sh));
         }
-        if (valid) { io.v_wait[j] = blocked ? 0 : (int32_t)s_wait[lane]; io.v_rule[j] = blocked && key ? s_rule[lane] : 0; }
+        // (s_wait is 0 on a lane without a key; a blocked entry keeps what the rules that passed it made it wait)
+        if (valid) { io.v_wait[j] = (int32_t)s_wait[lane]; io.v_rule[j] = blocked && key ? s_rule[lane] : 0; }
     }
     if (lane == 0) st.pm_init[res] = pm_init;
 }
@@ -1852,7 +1853,8 @@ __global__ void __launch_bounds__(256, SF_FILL_MINB) k_heavy_fill(DevState st, S
             e.c = g.c[k];
             if (!(g.f[k] & SF_EV_EXIT)) {
                 e.passed = (bits >> k) & 1u;
-                e.wait = ((rl || prm) && e.passed) ? wt[k] : 0;
+                // (a ParamFlow entry that a later rule blocks has slept in the throttle rules before it)
+                e.wait = (prm || (rl && e.passed)) ? wt[k] : 0;
                 if ((sysm >> k) & 1u) { e.status = sysblk_status(g.f[k]); vr[k] = (uint16_t)sysblk_rule(g.f[k]); }
                 else {
                     e.status = e.passed ? (e.wait > 0 ? SF_V_PASS_WAIT : SF_V_PASS) : (prm ? SF_V_BLOCK_PARAM : SF_V_BLOCK_FLOW);
