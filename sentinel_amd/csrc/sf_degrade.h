@@ -1,5 +1,5 @@
 // DegradeSlot circuit breakers on the GPU.
-// Device layout and launchers shared by sf_degrade.hip and sf_engine.cpp.
+// Device layout and launchers shared by sf_degrade.hip and sf_host_degrade.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -7,239 +7,16 @@
 // copy streams.  The entry points are serialised by a mutex (the Java shim
 // batches from many threads into one flusher).  There is no
 // CPU fallback: without a usable gfx950 device sf_create fails.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <mutex>
-#include <string>
-#include <vector>
-
-#include "sf_decide.h"
-#include "sf_pkargs.h"
-#include "sf_xflow.h"
-#include "sf_sysx.h"
-#include "sf_token.h"
-#include "sf_concur.h"
-#include "sf_wire.h"
-#include "sf_rls.h"
-#include "sf_degrade.h"
-#include "sf_mem.h"
-#include "sf_worksets.h"
-#include <rccl/rccl.h>
 #include <functional>
-#include <unordered_map>
 
-using namespace sf;
+#include "sf_host.h"
 
 static thread_local std::string g_err;
 
-static int fail(int code, const std::string& msg) {
+int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
-#define HIP_TRY(expr)                                                                   \
-    do {                                                                                \
-        hipError_t _e = (expr);                                                         \
-        if (_e != hipSuccess)                                                           \
-            return fail(_e == hipErrorOutOfMemory ? SF_ERR_NOMEM : SF_ERR_DEVICE,       \
-                        std::string(#expr ": ") + hipGetErrorString(_e));               \
-    } while (0)
-
-// The backend of sf_mem.h: the only place where device and pinned host memory
-// is allocated or freed.  Every pointer belongs to a DevPool: the engine's, a
-// slot's two, a work set's, or a call's scratch pool (freed when the call returns).
-static int hip_alloc_failed(const char* what, hipError_t e) {
-    return fail(SF_ERR_NOMEM, std::string(what) + ": " + hipGetErrorString(e));
-}
-static int hip_dev_alloc(void** p, size_t bytes) {
-    const hipError_t e = hipMalloc(p, bytes);
-    return e == hipSuccess ? SF_OK : hip_alloc_failed("hipMalloc", e);
-}
-static int hip_host_alloc(void** p, size_t bytes) {
-    const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
-    return e == hipSuccess ? SF_OK : hip_alloc_failed("hipHostMalloc", e);
-}
-static const MemOps HIP_MEM{hip_dev_alloc, [](void* p) { hipFree(p); }, hip_host_alloc, [](void* p) { hipHostFree(p); }};
-
-// cluster concurrency tokens (sf_concur.hip): the device state with the host's
-// view of it as of the last call
-struct CcHost {
-    CcState cs{};
-    CcWorkSet ws{HIP_MEM};
-    CcCounters ctr{};                 // device counters after the last call (ctr.top: free slots)
-    uint64_t grows = 0;
-    std::vector<sf_concurrent_config> cfg;    // sf_load_concurrent_config
-    GrowBuf stage, online;
-};
-
-// a device copy of host event arrays, remembered by their addresses (stage_in_events)
-struct StageBuf {
-    GrowBuf buf; const void* key[5] = {}; uint32_t n = 0;
-    int64_t fp[3] = {};                                     // ts[0], ts[n-1], flags[0] of the staged arrays
-    const uint8_t* st_src = nullptr; uint32_t st_n = 0;    // verdicts [0, st_n) of st_src already staged
-};
-
-// compact batches (sf_submit_packed): the device copy of the packed input of
-// one slot's batch, its SoA expansion and the verdicts copied back
-struct PkStage {
-    GrowBuf buf;
-    // ParamFlow arguments, elements, contexts (and staged origins), sized by the
-    // batch: [0, a_in) the staged sparse inputs (free at `consumed`), [a_in,
-    // a_in + a_x) what the expansion writes and the decide phase reads (free at
-    // the slot's `end`).  The boundary moves only when the buffer is reallocated.
-    GrowBuf abuf; size_t a_in = 0, a_x = 0;
-    hipEvent_t h2d = nullptr, d2h = nullptr;
-    hipEvent_t consumed = nullptr;     // the packed inputs expanded (the next H2D into them may start)
-    bool d2h_pending = false, consumed_pending = false;
-    const uint8_t* out_status = nullptr;   // host verdicts of the async batch in flight (sf_sync_packed)
-    int32_t* err_host = nullptr;           // its error flag, copied back with its verdicts (pinned)
-    // sf_sparse_verdicts of that batch: the caller's struct, the list lengths
-    // (pinned, copied back with the status bytes), the device lists
-    bool sparse = false;
-    sf_sparse_verdicts sp{};
-    uint32_t* sp_counts = nullptr;
-    const unsigned long long* sp_wl = nullptr; const unsigned long long* sp_rl = nullptr;
-};
-
-// Everything one batch in flight owns.  Batch k sorts into slot k % SF_SLOTS
-// while batch k-1 is decided; a synchronous batch does not advance the slot.
-// The count stays 2: the wait in take_slot ("two submits ago") and the packed
-// stage's reuse rules (submit_packed) are argued for two slots, and whether
-// the pipeline is correct with three is not established.
-constexpr int SF_SLOTS = 2;
-struct Slot {
-    Work w{};                       // the sorted-order buffers (allocated on first use: ready)
-    DevPool wpool{HIP_MEM};         // owns them
-    bool ready = false;
-    bool used = false;              // a batch has been enqueued into the slot (its events are recorded)
-    bool timed = false;             // that batch ran with timing on and is not yet in stats
-    hipEvent_t sorted = nullptr;    // its sort phase is enqueued (the decide streams wait for it)
-    hipEvent_t done = nullptr;      // its verdicts are scattered: the Work set is free
-    hipEvent_t end = nullptr;       // done and its ENTRY_NODE update (which reads the caller's batch)
-    hipEvent_t core = nullptr;      // its verdicts are written (the packed D2H copy waits for it)
-    hipEvent_t evs[SF_NUM_EVENTS]{};   // fork / join and timing events of its batch
-    PkStage pk;
-    DevPool pkpool{HIP_MEM};        // owns the packed stage's buffers
-    // [max_batch] effective flags of its batch (the AuthorityRule mark pass,
-    // sf_authority.hip), in wpool; allocated once rules are loaded.  Read by
-    // the batch up to `end`.
-    uint8_t* aflags = nullptr;
-};
-
-struct sf_engine {
-    sf_config cfg{};
-    // owns everything below that has no pool of its own: the state tables, the
-    // rule tables, the staging buffers, the origin / context node pool
-    DevPool pool{HIP_MEM};
-    DevPool user_dev{HIP_MEM}, user_host{HIP_MEM};   // sf_device_alloc / sf_host_alloc
-    hipStream_t stream = nullptr, stream2 = nullptr, stream3 = nullptr, stream4 = nullptr;   // 4: the wave walk
-    hipStream_t sstream = nullptr;  // sort phase of the next batch (overlaps the decide phase on `stream`)
-    // ENTRY_NODE's update of an asynchronous batch (after its verdicts, beside
-    // the next batch's decide phase: decisions read ENTRY_NODE only with
-    // SystemRules, whose batches are synchronous); ev_en: the last one enqueued,
-    // en_async: `stream` is not yet ordered after it (en_fence)
-    hipStream_t enstream = nullptr;
-    bool en_own = false;            // enstream is a stream of its own (else one of the decide streams)
-    int side_mode = 3;
-    hipEvent_t ev_en = nullptr;
-    bool en_async = false;
-    bool serial = false;            // diagnostics (SF_SERIAL_STREAMS=1): every kernel on one stream
-    uint32_t R = 0, key_bits = 1;
-    DevState st{};
-    Slot slot[SF_SLOTS];
-    int cur = 0, last = 0;          // slot of the next / last submitted batch
-    unsigned pending = 0;           // slots (bit k) with an asynchronous batch not yet checked by sf_sync
-    SysRule sys{};                  // SystemRuleManager statics; sys.check: batches go through the planner
-    SysPlanDev* sys_plan = nullptr; SysExitQ* sys_pa = nullptr; SysEntQ* sys_pb = nullptr;
-    uint8_t* sys_ibuf = nullptr;                  // the planner's inert flags (sys_plan)
-    uint8_t* sys_mask = nullptr;    // [max_batch] planner verdicts (sf_system.h)
-    // rules
-    std::vector<uint32_t> flow_pos;        // loaded valid rule index -> CSR position
-    uint32_t n_flow = 0, n_prule = 0;
-    AuthTables auth{};                     // AuthorityRule tables in `pool` (auth.of null: no rule loaded)
-    // the exact ParamFlow table's fill (param_reserve): inserts counted on the
-    // device (st.pins), as of the last drain; upper bound of the inserts of
-    // batches enqueued since; the most keys one event can insert
-    uint64_t p_used = 0, p_pending = 0, p_kmax = 0, p_grows = 0;
-    // staging for host-memory batches
-    GrowBuf stage_in, stage_out;
-    StageBuf plan_sb, en_sb;                       // sf_system_plan / sf_entry_node_add inputs
-    bool timing = false;
-    sf_stats stats{};
-    std::mutex mu;
-    // cluster token server (sf_token.hip)
-    TokState ts{};
-    TokWorkSet tw{HIP_MEM};
-    std::vector<sf_namespace> host_ns;
-    std::vector<sf_cluster_flow_rule> host_cflow;
-    std::vector<sf_cluster_param_rule> host_cparam;
-    std::vector<sf_hot_item> host_citems;
-    std::vector<int64_t> cflow_ids;           // flow rule index -> flowId
-    GrowBuf tok_stage;
-    CcHost cc;
-    int64_t* d_sum = nullptr;
-    GrowBuf wire_arena;                                  // sf_serve_frames scratch
-    // Envoy rate-limit service (sf_rls.hip): decided on ts / tw above
-    RlsWorkSet rlw{HIP_MEM};
-    GrowBuf rls_stage;
-    uint32_t* rls_len = nullptr;                         // [3] table lengths of a device-memory batch
-    uint32_t rls_wave_min = RLS_WAVE_MIN;                // diagnostics (SF_RLS_WAVE=0): every segment on the lane route
-    sf_rls_stats rls_stats{};
-    // ENTRY_NODE and the metric snapshot (sf_entry.hip)
-    EntryNode* en = nullptr;
-    EntryAcc* en_acc = nullptr;
-    // sf_set_report_entry_node: the ENTRY_NODE sf_metric_log writes (node-wide merge), host copy
-    bool report_set = false;
-    EntryNode report{};
-    EntryNode* en_report = nullptr;    // device staging of `report` for the metric kernels
-    uint32_t* snap_counts = nullptr; uint32_t* snap_offsets = nullptr; uint32_t* snap_total = nullptr;
-    void* snap_scan = nullptr; size_t snap_scan_bytes = 0;
-    bool snap_ready = false;           // the four above are allocated
-    GrowBuf snap_rows;
-    // metrics.log (sf_metric.hip)
-    char* nm_bytes = nullptr; uint64_t* nm_off = nullptr; int32_t* nm_types = nullptr; uint32_t n_names = 0;
-    struct MetricLog {                 // ml_reserve: the per-node buffers (ready) and the per-row ones (row_cap)
-        unsigned long long* mask = nullptr; uint32_t* counts = nullptr; uint32_t* offsets = nullptr;
-        uint32_t* total = nullptr; uint64_t* bytes = nullptr;
-        bool ready = false;
-        sf_metric_row* rows = nullptr; uint8_t* keys = nullptr; uint32_t* order = nullptr;
-        uint64_t* len = nullptr; uint64_t* off = nullptr; uint32_t row_cap = 0;
-        GrowBuf out, tmp;
-    } ml;
-    DevPool ml_pool{HIP_MEM};
-    hipEvent_t ml_ev[3]{};
-    // node-wide aggregate over the ranks of a node (RCCL over xGMI)
-    ncclComm_t comm = nullptr;
-    // sharded SystemRules, the per-window exchange (sf_sysx.h, sf_submit_node)
-    int64_t* sx_msg = nullptr;            // this rank's message [SX_WORDS] (+ the setup words)
-    GrowBuf sx_recv;
-    int64_t* sx_seq = nullptr;            // [max_batch] device copy of host sequence numbers
-    uint8_t* sx_ibuf = nullptr;           // [max_batch] inert flags of the round
-    std::vector<int64_t> sx_hsend, sx_hrecv;   // host side of a callback all-gather
-    int64_t* sxw_msg = nullptr;           // the wide kinds: this rank's message [SXW_WORDS]
-    SxwSeg* sxw_segs = nullptr;           // [SXW_MAX_SEGS] device copy of a round's settled runs
-    std::vector<SxwSeg> sxw_hsegs;
-    int64_t* agg = nullptr;               // [ws (S+60) | gws (S+60) | vals ((S+60)*6+1) | minrt (S+60)]
-    // DegradeSlot circuit breakers (sf_degrade.hip)
-    DegradeDev dg{};
-    DegradeWorkSet dgw{HIP_MEM};
-    std::vector<uint32_t> dg_pos;         // breaker index (load order) -> CSR position
-    std::vector<sf_degrade_rule> dg_rules;   // the valid rules of the loaded breakers (load order)
-    GrowBuf dg_stage;
-    // xflow walk (sf_xflow.h): group keys and the origin / context node pool
-    uint32_t* xmap_buf = nullptr;
-    uint8_t* xw_buf = nullptr;
-    // the pool's chunks (host mirror of the device directory st.ax_chunks) and
-    // the index table's growth (sf_origin.hip); counts for sf_stats
-    std::vector<AuxChunk> ax_host;
-    AuxChunk* ax_dir = nullptr;
-    uint64_t aux_grows = 0;
-    // copy streams of compact batches (PkStage): H2D(k+1), decide(k) and D2H(k-1) overlap
-    hipStream_t h2d = nullptr, d2h = nullptr;
-    int32_t* rh_err = nullptr;            // rehash_table's overflow flag
-};
 
 extern "C" {
 
@@ -270,7 +47,7 @@ void sf_destroy(sf_engine* e) {
     if (!e) return;
     for (hipStream_t x : {e->sstream, e->stream, e->h2d, e->d2h}) if (x) hipStreamSynchronize(x);
     for (Slot& sl : e->slot) { sl.wpool.clear(); sl.pkpool.clear(); }
-    for (DevPool* p : {&e->pool, &e->user_dev, &e->user_host, &e->tw.pool, &e->rlw.pool, &e->cc.ws.pool, &e->dgw.pool, &e->ml_pool})
+    for (DevPool* p : {&e->pool, &e->user_dev, &e->user_host, &e->tok.tw.pool, &e->rls.ws.pool, &e->cc.ws.pool, &e->dg.ws.pool, &e->rep.ml_pool})
         p->clear();
     if (e->comm) ncclCommDestroy(e->comm);
     for (Slot& sl : e->slot) {
@@ -278,7 +55,7 @@ void sf_destroy(sf_engine* e) {
         for (hipEvent_t x : {p.h2d, p.d2h, p.consumed, sl.sorted, sl.done, sl.end, sl.core}) if (x) hipEventDestroy(x);
         for (hipEvent_t x : sl.evs) if (x) hipEventDestroy(x);
     }
-    for (auto& x : e->ml_ev) if (x) hipEventDestroy(x);
+    for (auto& x : e->rep.ml_ev) if (x) hipEventDestroy(x);
     if (e->ev_en) hipEventDestroy(e->ev_en);
     for (hipStream_t x : {e->h2d, e->d2h, e->stream, e->stream2, e->stream3, e->stream4, e->sstream}) if (x) hipStreamDestroy(x);
     if (e->enstream && e->en_own) hipStreamDestroy(e->enstream);
@@ -410,7 +187,7 @@ static int create(sf_engine* e) {
         else HIP_TRY(hipStreamCreateWithFlags(&e->sstream, hipStreamNonBlocking));
     }
     if (const char* v = getenv("SF_SERIAL_STREAMS")) e->serial = v[0] == '1';
-    if (const char* v = getenv("SF_RLS_WAVE")) if (v[0] == '0') e->rls_wave_min = UINT32_MAX;
+    if (const char* v = getenv("SF_RLS_WAVE")) if (v[0] == '0') e->rls.wave_min = UINT32_MAX;
     {   // the side stream of asynchronous batches: stream C, whose light lanes end
         // first (diagnostics SF_SIDE: 0 none -- on `stream` as before round 6 --,
         // 1 a stream of its own, 2 stream B, 3 stream C).  Same-box means of the
@@ -459,11 +236,11 @@ static int create(sf_engine* e) {
     HIP_TRY(hipMemsetAsync(st.pins, 0, 256 * 16 * sizeof(unsigned int), e->stream));
     HIP_TRY(hipMemsetAsync(st.err, 0, sizeof(int32_t), e->stream));
     HIP_TRY(launch_init_state(st, e->stream));
-    e->ts.err = st.err;
-    e->ts.exceed_count = c.exceed_count;
-    e->ts.shard_count = c.shard_count; e->ts.shard_index = c.shard_index;
-    e->ts.max_occupy_ratio = c.max_occupy_ratio;
-    SF_TRY(e->pool.alloc(&e->d_sum, nz(sizeof(int64_t))));
+    e->tok.ts.err = st.err;
+    e->tok.ts.exceed_count = c.exceed_count;
+    e->tok.ts.shard_count = c.shard_count; e->tok.ts.shard_index = c.shard_index;
+    e->tok.ts.max_occupy_ratio = c.max_occupy_ratio;
+    SF_TRY(e->pool.alloc(&e->tok.d_sum, nz(sizeof(int64_t))));
     SF_TRY(e->pool.alloc(&st.last_fetch, nz(R * sizeof(int64_t))));
     SF_TRY(e->pool.alloc(&st.last_ts, nz(sizeof(int64_t))));
     {
@@ -480,7 +257,7 @@ static int create(sf_engine* e) {
     return SF_OK;
 }
 
-static int local_of(const sf_engine* e, uint32_t res, uint32_t* l) {
+extern "C++" int local_of(const sf_engine* e, uint32_t res, uint32_t* l) {
     if (res % e->cfg.shard_count != e->cfg.shard_index) return 0;
     *l = res / e->cfg.shard_count;
     return *l < e->R;
@@ -525,7 +302,7 @@ static int batch_error(int err) {
 
 // order `stream` after the last asynchronous ENTRY_NODE update (every host
 // call that reads or writes ENTRY_NODE on `stream` does this first)
-static int en_fence(sf_engine* e) {
+extern "C++" int en_fence(sf_engine* e) {
     if (!e->en_async) return SF_OK;
     HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_en, 0));
     e->en_async = false;
@@ -537,7 +314,7 @@ static int sparse_complete(PkStage& pk);
 // the first error flag raised by any of them.  An async packed batch whose
 // verdicts the caller has not collected keeps its error for its own
 // sf_sync_packed, unless `all` (sf_sync: every batch collected here).
-static int drain(sf_engine* e, bool all = false) {
+extern "C++" int drain(sf_engine* e, bool all) {
     if (e->en_async) { HIP_TRY(hipStreamSynchronize(e->enstream)); e->en_async = false; }
     if (!e->pending) return SF_OK;
     HIP_TRY(hipStreamSynchronize(e->sstream));
@@ -964,7 +741,7 @@ int sf_set_system_status(sf_engine* e, double avg_load, double cpu_usage) {
 
 // ---------------------------------------------------------------- AuthorityRule (sf_authority.h)
 // the slot's effective-flags array, with its Work set's pool
-static int slot_aflags(sf_engine* e, Slot& sl) {
+extern "C++" int slot_aflags(sf_engine* e, Slot& sl) {
     if (sl.aflags) return SF_OK;
     return sl.wpool.alloc(&sl.aflags, nz(e->cfg.max_batch));
 }
@@ -1032,15 +809,18 @@ int sf_authority_mark(sf_engine* e, const uint32_t* res_id, const uint32_t* orig
         return SF_OK;
     }
     DevPool tmp{HIP_MEM};
-    uint32_t *d_res = nullptr, *d_og = nullptr;
-    uint8_t *d_fl = nullptr, *d_out = nullptr;
-    SF_TRY(tmp.alloc(&d_res, (size_t)n * 4)); SF_TRY(tmp.alloc(&d_og, (size_t)n * 4));
-    SF_TRY(tmp.alloc(&d_fl, n)); SF_TRY(tmp.alloc(&d_out, n));
-    HIP_TRY(hipMemcpyAsync(d_res, res_id, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_og, origin, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_fl, flags, n, hipMemcpyHostToDevice, s));
+    GrowBuf buf;
+    const uint32_t *d_res = nullptr, *d_og = nullptr;
+    const uint8_t* d_fl = nullptr;
+    uint8_t* d_out = nullptr;
+    StagePlan plan(true, true);
+    plan.in(true, &d_res, res_id, (size_t)n * 4); plan.in(true, &d_og, origin, (size_t)n * 4);
+    plan.in(true, &d_fl, flags, n); plan.out(true, &d_out, out_flags, n);
+    SF_TRY(buf.reserve(tmp, plan.size()));
+    plan.bind(buf.p);
+    SF_TRY(plan.upload(h2d_on(s)));
     HIP_TRY(launch_auth_mark(t, d_res, d_og, d_fl, n, (uint8_t)SF_EV_BLOCKED, d_out, s));
-    HIP_TRY(hipMemcpyAsync(out_flags, d_out, n, hipMemcpyDeviceToHost, s));
+    SF_TRY(plan.download(d2h_on(s)));
     HIP_TRY(hipStreamSynchronize(s));
     return SF_OK;
 }
@@ -1102,63 +882,37 @@ static int param_reserve(sf_engine* e, uint64_t bound) {
 
 // the caller's batch and verdict arrays as device pointers: host arrays are
 // copied to the engine's staging buffers on stream ss (verdicts come back
-// from stage_out after the decision)
+// from stage_out after the decision: vout.download, finish_sync)
 static int stage_batch(sf_engine* e, const sf_event_batch* in, const sf_verdicts* out, hipStream_t ss,
-                       DevBatch& b, DevVerdicts& dv) {
+                       DevBatch& b, DevVerdicts& dv, StagePlan& vout) {
     const uint32_t n = in->n;
     b.n = n; b.arg_slots = in->arg_slots; b.arg_stride = n;
-    if (in->mem == SF_MEM_HOST) {
-        Layout L;
-        const bool coll = in->arg_elem_off != nullptr;
-        const size_t o_res = L.take((size_t)n * 4), o_ts = L.take((size_t)n * 8), o_cnt = L.take((size_t)n * 4);
-        const size_t o_fl = L.take(n), o_er = L.take_if(in->entry_ref, (size_t)n * 8);
-        const size_t o_ct = L.take_if(in->entry_ref && in->create_ts, (size_t)n * 8), o_na = L.take_if(in->n_args, n);
-        // (the argument arrays have their room with or without arguments)
-        const size_t o_at = L.take((size_t)n * in->arg_slots), o_ab = L.take((size_t)n * in->arg_slots * 8);
-        const size_t o_eo = L.take_if(coll, ((size_t)n * in->arg_slots + 1) * 4), o_et = L.take_if(coll, in->n_elems);
-        const size_t o_eb = L.take_if(coll, (size_t)in->n_elems * 8), o_og = L.take_if(in->origin, (size_t)n * 4);
-        const size_t o_cx = L.take_if(in->context, (size_t)n * 4);
-        SF_TRY(e->stage_in.reserve(e->pool, L.size()));
-        char* base = e->stage_in.at(0);
-        auto up = [&](size_t off, const void* src, size_t bytes) -> const void* {
-            if (!src || !bytes) return nullptr;
-            hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, ss);
-            return base + off;
-        };
-        b.res = (const uint32_t*)up(o_res, in->res_id, (size_t)n * 4);
-        b.ts = (const int64_t*)up(o_ts, in->ts_ms, (size_t)n * 8);
-        b.cnt = (const int32_t*)up(o_cnt, in->count, (size_t)n * 4);
-        b.flags = (const uint8_t*)up(o_fl, in->flags, n);
-        b.eref = (const int64_t*)up(o_er, in->entry_ref, in->entry_ref ? (size_t)n * 8 : 0);
-        b.cts = (const int64_t*)up(o_ct, in->entry_ref ? in->create_ts : nullptr, (size_t)n * 8);
-        b.nargs = (const uint8_t*)up(o_na, in->n_args, n);
-        b.atag = (const uint8_t*)up(o_at, in->arg_tag, (size_t)n * in->arg_slots);
-        b.abits = (const uint64_t*)up(o_ab, in->arg_bits, (size_t)n * in->arg_slots * 8);
-        if (coll) {
-            b.aoff = (const uint32_t*)up(o_eo, in->arg_elem_off, ((size_t)n * in->arg_slots + 1) * 4);
-            b.etag = (const uint8_t*)up(o_et, in->elem_tag, in->n_elems);
-            b.ebits = (const uint64_t*)up(o_eb, in->elem_bits, (size_t)in->n_elems * 8);
-        }
-        b.origin = (const uint32_t*)up(o_og, in->origin, (size_t)n * 4);
-        b.ctx = (const uint32_t*)up(o_cx, in->context, (size_t)n * 4);
-    } else {
-        b.res = in->res_id; b.ts = in->ts_ms; b.cnt = in->count; b.flags = in->flags;
-        b.eref = in->entry_ref; b.cts = in->entry_ref ? in->create_ts : nullptr;
-        b.nargs = in->n_args; b.atag = in->arg_tag; b.abits = in->arg_bits;
-        b.aoff = in->arg_elem_off; b.etag = in->elem_tag; b.ebits = in->elem_bits;
-        b.origin = in->origin; b.ctx = in->context;
-    }
-    if (out->mem == SF_MEM_HOST) {
-        Layout L;
-        const size_t o_st = L.take(n), o_wt = L.take((size_t)n * 4), o_ru = L.take((size_t)n * 2);
-        SF_TRY(e->stage_out.reserve(e->pool, L.size()));
-        char* base = e->stage_out.at(0);
-        dv.status = (uint8_t*)(base + o_st);
-        dv.wait = out->wait_ms ? (int32_t*)(base + o_wt) : nullptr;
-        dv.rule = out->rule_idx ? (uint16_t*)(base + o_ru) : nullptr;
-    } else {
-        dv.status = out->status; dv.wait = out->wait_ms; dv.rule = out->rule_idx;
-    }
+    const bool host = in->mem == SF_MEM_HOST, coll = in->arg_elem_off != nullptr;
+    const size_t na = (size_t)n * in->arg_slots;
+    StagePlan p(host, false);
+    // a host array that is absent or empty gives a null pointer; a device array is passed on as it is
+    const auto arr = [&](bool on, auto** dev, const void* src, size_t bytes) {
+        p.in(on && (!host || (src && bytes)), dev, src, bytes);
+    };
+    arr(true, &b.res, in->res_id, (size_t)n * 4); arr(true, &b.ts, in->ts_ms, (size_t)n * 8);
+    arr(true, &b.cnt, in->count, (size_t)n * 4); arr(true, &b.flags, in->flags, n);
+    arr(true, &b.eref, in->entry_ref, (size_t)n * 8);
+    arr(in->entry_ref != nullptr, &b.cts, in->create_ts, (size_t)n * 8);
+    arr(true, &b.nargs, in->n_args, n);
+    arr(true, &b.atag, in->arg_tag, na); arr(true, &b.abits, in->arg_bits, na * 8);
+    // (a host batch without arg_elem_off has no element arrays)
+    arr(!host || coll, &b.aoff, in->arg_elem_off, (na + 1) * 4);
+    arr(!host || coll, &b.etag, in->elem_tag, in->n_elems);
+    arr(!host || coll, &b.ebits, in->elem_bits, (size_t)in->n_elems * 8);
+    arr(true, &b.origin, in->origin, (size_t)n * 4); arr(true, &b.ctx, in->context, (size_t)n * 4);
+    SF_TRY(e->stage_in.reserve(e->pool, p.size()));
+    p.bind(e->stage_in.p);
+    SF_TRY(p.upload(h2d_on(ss)));
+    vout.out(true, &dv.status, out->status, n);
+    vout.out(out->wait_ms != nullptr, &dv.wait, out->wait_ms, (size_t)n * 4);
+    vout.out(out->rule_idx != nullptr, &dv.rule, out->rule_idx, (size_t)n * 2);
+    SF_TRY(e->stage_out.reserve(e->pool, vout.size()));
+    vout.bind(e->stage_out.p);
     return SF_OK;
 }
 
@@ -1214,20 +968,17 @@ static void slot_enqueued(sf_engine* e, Slot& sl, uint32_t n) {
 }
 
 // The end of a synchronous batch on `stream`: its events, the verdicts back to
-// host arrays, its error flag, one stream sync.  plain: not the SystemRule
-// rounds (the segment count and kernel times of the batch go to the stats).
-static int finish_sync(sf_engine* e, Slot& sl, const sf_verdicts* out, const DevVerdicts& dv, uint32_t n, bool plain) {
+// host arrays (vout: stage_batch's), its error flag, one stream sync.  plain:
+// not the SystemRule rounds (the segment count and kernel times of the batch
+// go to the stats).
+static int finish_sync(sf_engine* e, Slot& sl, const StagePlan& vout, uint32_t n, bool plain) {
     hipStream_t s = e->stream;
     HIP_TRY(hipEventRecord(sl.core, s));
     HIP_TRY(hipEventRecord(sl.done, s));
     HIP_TRY(hipEventRecord(sl.end, s));
     slot_enqueued(e, sl, n);
     sl.timed = plain && e->timing;
-    if (out->mem == SF_MEM_HOST && n) {
-        HIP_TRY(hipMemcpyAsync(out->status, dv.status, n, hipMemcpyDeviceToHost, s));
-        if (dv.wait) HIP_TRY(hipMemcpyAsync(out->wait_ms, dv.wait, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        if (dv.rule) HIP_TRY(hipMemcpyAsync(out->rule_idx, dv.rule, (size_t)n * 2, hipMemcpyDeviceToHost, s));
-    }
+    SF_TRY(vout.download(d2h_on(s)));
     int32_t err = 0;
     uint32_t nseg = 0;
     HIP_TRY(hipMemcpyAsync(&err, sl.w.err, 4, hipMemcpyDeviceToHost, s));
@@ -1284,7 +1035,7 @@ struct PackedHook { PreSort pre; bool acsr; uint32_t n_arg_events; };
 // safe sub-batches (sf_system.h), each planned on the exact ENTRY_NODE, then
 // sorted / decided / reduced by the ordinary pipeline.  One host round trip
 // per sub-batch (its end q).
-static int submit_sys_rounds(sf_engine* e, Slot& sl, const DevBatch& staged, const DevVerdicts& dv, const sf_verdicts* out,
+static int submit_sys_rounds(sf_engine* e, Slot& sl, const DevBatch& staged, const DevVerdicts& dv, const StagePlan& vout,
                              bool with_ox, const PreSort* pre) {
     DevBatch b = staged;                                // (the mark pass below redirects its flags)
     const uint32_t n = b.n;
@@ -1325,7 +1076,7 @@ static int submit_sys_rounds(sf_engine* e, Slot& sl, const DevBatch& staged, con
         rounds++;
     }
     e->stats.sys_rounds += rounds;
-    return finish_sync(e, sl, out, dv, n, false);
+    return finish_sync(e, sl, vout, n, false);
 }
 
 static int submit_core(sf_engine* e, const sf_event_batch* in, sf_verdicts* out, bool async,
@@ -1359,7 +1110,8 @@ static int submit_core(sf_engine* e, const sf_event_batch* in, sf_verdicts* out,
     Work& w = sl.w;
     DevBatch b{};
     DevVerdicts dv{};
-    SF_TRY(stage_batch(e, in, out, ss, b, dv));
+    StagePlan vout(false, out->mem == SF_MEM_HOST);
+    SF_TRY(stage_batch(e, in, out, ss, b, dv, vout));
     b.acsr = hook && hook->acsr;
     if (forced) {
         // the forced SystemRule verdicts of this (sub-)batch, planned node-wide
@@ -1367,7 +1119,7 @@ static int submit_core(sf_engine* e, const sf_event_batch* in, sf_verdicts* out,
         HIP_TRY(hipMemcpyAsync(e->sys_mask, forced, n, hipMemcpyHostToDevice, ss));
         b.sys = e->sys_mask;
     }
-    if (e->sys.check && !forced) return submit_sys_rounds(e, sl, b, dv, out, with_ox, pre);
+    if (e->sys.check && !forced) return submit_sys_rounds(e, sl, b, dv, vout, with_ox, pre);
     // sort phase on the sort stream, into this batch's Work set (after the
     // decide phase of the batch that used it last; the mark pass rewrites the
     // flags that batch's ENTRY_NODE update reads)
@@ -1405,7 +1157,7 @@ static int submit_core(sf_engine* e, const sf_event_batch* in, sf_verdicts* out,
         le = launch_entry_node(stl, b, dv.status, e->en, e->en_acc, s);
         if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("entry node: ") + hipGetErrorString(le));
     }
-    if (!async) return finish_sync(e, sl, out, dv, n, true);
+    if (!async) return finish_sync(e, sl, vout, n, true);
     // side: on the side stream after the scatter.  The Work set is free after
     // the scatter (done: the sort of the batch after next waits for it), the
     // batch k_entry_acc reads after the update (end)
@@ -1536,33 +1288,43 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
     // this slot waits only for `consumed`.
     const bool args = ai.n_arg_events != 0, ctx = in->context != nullptr, og_copy = host_in && in->origin;
     const uint32_t nae = ai.n_arg_events, nv = ai.n_values, ne = ai.n_elems, slots = args ? ai.arg_slots : 0;
-    const bool st = host_in;                                   // staged inputs (device batches are read in place)
-    Layout LI, LX;
-    const size_t i_ae = LI.take_if(st && args && ai.arg_event, (size_t)nae * 4), i_ao = LI.take_if(st && args && ai.arg_off, ((size_t)nae + 1) * 4);
-    const size_t i_at = LI.take_if(st && nv, nv), i_ab = LI.take_if(st && nv, (size_t)nv * 8);
-    const size_t i_eo = LI.take_if(st && ai.elem_off, ((size_t)nv + 1) * 4), i_et = LI.take_if(st && ne, ne), i_eb = LI.take_if(st && ne, (size_t)ne * 8);
-    const size_t i_cx = LI.take_if(st && ctx, (size_t)n * 4);
-    const size_t x_na = LX.take_if(args, n), x_at = LX.take_if(args, (size_t)n * slots), x_ab = LX.take_if(args, (size_t)n * slots * 8);
-    const size_t x_eo = LX.take_if(ai.elem_off, ((size_t)nv + 1) * 4), x_et = LX.take_if(ne, ne), x_eb = LX.take_if(ne, (size_t)ne * 8);
-    const size_t x_cx = LX.take_if(ctx, (size_t)n * 4), x_og = LX.take_if(og_copy, (size_t)n * 4);
-    if (LI.size() > pk.a_in || LX.size() > pk.a_x) {
+    // staged inputs (device batches are read in place: the sources of the
+    // expansion are the caller's device arrays, or the staged ones); a host
+    // array that is absent or empty gives a null pointer
+    StagePlan pi(host_in, false), px(false, false);
+    const auto arr = [&](auto** dev, size_t bytes) {     // (staged in place of the caller's pointer)
+        pi.in(!host_in || (*dev && bytes), dev, *dev, bytes);
+    };
+    PkCopy cp{};
+    if (args) {
+        arr(&ai.arg_event, (size_t)nae * 4); arr(&ai.arg_off, ((size_t)nae + 1) * 4);
+        arr(&ai.arg_tag, nv); arr(&ai.arg_bits, (size_t)nv * 8);
+        arr(&ai.elem_off, ((size_t)nv + 1) * 4);
+    }
+    pi.in(ne != 0, &cp.etag, in->elem_tag, ne); pi.in(ne != 0, &cp.ebits, in->elem_bits, (size_t)ne * 8);
+    pi.in(ctx, &cp.ctx, in->context, (size_t)n * 4);
+    // what the expansion writes
+    PkArgOut ao{};
+    px.scratch(args, &ao.nargs, n); px.scratch(args, &ao.atag, (size_t)n * slots);
+    px.scratch(args, &ao.abits, (size_t)n * slots * 8);
+    px.scratch(args && ai.elem_off, &ao.eoff, ((size_t)nv + 1) * 4);
+    px.scratch(ne != 0, &cp.etag_out, ne); px.scratch(ne != 0, &cp.ebits_out, (size_t)ne * 8);
+    px.scratch(ctx, &cp.ctx_out, (size_t)n * 4); px.scratch(og_copy, &cp.origin_out, (size_t)n * 4);
+    if (pi.size() > pk.a_in || px.size() > pk.a_x) {
         SF_TRY(pk_quiesce(sl));
         // (both regions grow to the largest seen: the boundary moves only here)
-        const size_t c_in = std::max(LI.size(), pk.a_in), c_x = std::max(LX.size(), pk.a_x);
+        const size_t c_in = std::max(pi.size(), pk.a_in), c_x = std::max(px.size(), pk.a_x);
         pk.a_in = pk.a_x = 0;
         SF_TRY(pk.abuf.reserve(sl.pkpool, c_in + c_x));
         pk.a_in = c_in; pk.a_x = c_x;
     }
-    char* AI = pk.abuf.at(0);                                  // staged inputs
-    // the expanded region (no buffer: the batch needs none, and no offset is taken)
-    auto ax = [&](bool on, size_t o) -> char* { return on && pk.abuf.p ? pk.abuf.at(pk.a_in + o) : nullptr; };
+    pi.bind(pk.abuf.p);
+    px.bind(pk.abuf.at(pk.a_in));
     hipStream_t ss = e->serial ? e->stream : e->sstream;
     const uint64_t* ev = in->ev; const int64_t* xr = in->exit_ref; const int64_t* xc = in->exit_cts;
     const uint32_t* ev4 = narrow ? in->ev4 : nullptr; const uint32_t* mse = narrow ? in->ms_end : nullptr;
     const uint32_t n_ms = narrow ? in->n_ms : 0;
     const int32_t* ce = in->count_ext; const uint32_t* og = in->origin;
-    PkCopy cp{};                                               // sources: the caller's device arrays, or the staged ones
-    cp.etag = ne ? in->elem_tag : nullptr; cp.ebits = ne ? in->elem_bits : nullptr; cp.ctx = in->context;
     if (host_in) {
         hipStream_t h = e->serial ? e->stream : e->h2d;
         if (pk.consumed_pending) HIP_TRY(hipStreamWaitEvent(h, pk.consumed, 0));
@@ -1591,24 +1353,7 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
             HIP_TRY(hipMemcpyAsync(B + o_og, in->origin, (size_t)n * 4, hipMemcpyHostToDevice, h));
             og = (const uint32_t*)(B + o_og);
         }
-        hipError_t ue = hipSuccess;
-        auto up = [&](size_t o, const void* src, size_t bytes) -> const void* {
-            if (!src || !bytes) return nullptr;
-            const hipError_t he = hipMemcpyAsync(AI + o, src, bytes, hipMemcpyHostToDevice, h);
-            if (he != hipSuccess) ue = he;
-            return AI + o;
-        };
-        if (args) {
-            ai.arg_event = (const uint32_t*)up(i_ae, in->arg_event, (size_t)nae * 4);
-            ai.arg_off = (const uint32_t*)up(i_ao, in->arg_off, ((size_t)nae + 1) * 4);
-            ai.arg_tag = (const uint8_t*)up(i_at, in->arg_tag, nv);
-            ai.arg_bits = (const uint64_t*)up(i_ab, in->arg_bits, (size_t)nv * 8);
-            ai.elem_off = (const uint32_t*)up(i_eo, ai.elem_off, ((size_t)nv + 1) * 4);
-        }
-        cp.etag = (const uint8_t*)up(i_et, ne ? in->elem_tag : nullptr, ne);
-        cp.ebits = (const uint64_t*)up(i_eb, ne ? in->elem_bits : nullptr, (size_t)ne * 8);
-        cp.ctx = (const uint32_t*)up(i_cx, in->context, (size_t)n * 4);
-        if (ue != hipSuccess) return fail(SF_ERR_DEVICE, std::string("packed H2D: ") + hipGetErrorString(ue));
+        SF_TRY(pi.upload(h2d_on(h)));
         if (og_copy) cp.origin = og;
         HIP_TRY(hipEventRecord(pk.h2d, h));
         HIP_TRY(hipStreamWaitEvent(ss, pk.h2d, 0));
@@ -1618,10 +1363,6 @@ static int submit_packed(sf_engine* e, const sf_packed_batch* in, sf_verdicts* o
     const uint32_t n_exit = in->n_exit, n_cext = in->n_count_ext;
     const hipEvent_t consumed = pk.consumed;
     if (!args) { ai.n_arg_events = ai.n_values = 0; ai.arg_event = ai.arg_off = nullptr; ai.elem_off = nullptr; }
-    const PkArgOut ao{(uint8_t*)ax(args, x_na), (uint8_t*)ax(args, x_at), (uint64_t*)ax(args, x_ab),
-                      (uint32_t*)ax(ai.elem_off != nullptr, x_eo)};
-    cp.etag_out = (uint8_t*)ax(ne != 0, x_et); cp.ebits_out = (uint64_t*)ax(ne != 0, x_eb);
-    cp.ctx_out = (uint32_t*)ax(ctx, x_cx); cp.origin_out = (uint32_t*)ax(og_copy, x_og);
     const PreSort expand = [=](hipStream_t st_, int32_t* err) {
         const hipError_t le = launch_pk_expand(ev, ev4, mse, n_ms, xr, xc, ce, base, n, n_exit, n_cext, (uint2*)(B + o_tc),
                                                (uint32_t*)(B + o_res), (int64_t*)(B + o_ts), (int32_t*)(B + o_cnt),
@@ -1759,26 +1500,27 @@ int sf_submit_forced(sf_engine* e, const sf_event_batch* in, sf_verdicts* out, c
 static int stage_in_events(sf_engine* e, StageBuf& sb, const sf_event_batch* in, const uint8_t* status,
                            uint32_t n_status, DevBatch& b, uint8_t** dstatus, bool keep = false) {
     const uint32_t n = in->n;
-    Layout L;
-    const size_t o_ts = L.take((size_t)n * 8), o_cnt = L.take((size_t)n * 4), o_fl = L.take(n);
-    const size_t o_er = L.take((size_t)n * 8), o_ct = L.take((size_t)n * 8), o_st = L.take((size_t)n + 1);
+    b = DevBatch{};
+    b.n = n;
+    StagePlan p(true, false);
+    p.in(true, &b.ts, in->ts_ms, (size_t)n * 8); p.in(true, &b.cnt, in->count, (size_t)n * 4);
+    p.in(true, &b.flags, in->flags, n);
+    p.in(in->entry_ref != nullptr, &b.eref, in->entry_ref, (size_t)n * 8);
+    p.in(in->create_ts != nullptr, &b.cts, in->create_ts, (size_t)n * 8);
+    p.scratch(dstatus, (size_t)n + 1);
     const void* key[5] = {in->ts_ms, in->count, in->flags, in->entry_ref, in->create_ts};
     // the same host arrays as the round before: a cheap fingerprint of their
     // contents must match too (the contract is that the caller only appends
     // verdicts between rounds; an edited event array is restaged, not trusted)
     const int64_t fp[3] = {n ? in->ts_ms[0] : 0, n ? in->ts_ms[n - 1] : 0, n ? (int64_t)in->flags[0] : 0};
     keep = keep && sb.buf.p && sb.n == n && std::equal(key, key + 5, sb.key) && std::equal(fp, fp + 3, sb.fp) &&
-           L.size() <= sb.buf.bytes;
-    if (L.size() > sb.buf.bytes) sb.n = 0;         // (nothing is staged in a new buffer)
-    SF_TRY(sb.buf.reserve(e->pool, L.size()));
-    char* base = sb.buf.at(0);
+           p.size() <= sb.buf.bytes;
+    if (p.size() > sb.buf.bytes) sb.n = 0;         // (nothing is staged in a new buffer)
+    SF_TRY(sb.buf.reserve(e->pool, p.size()));
+    p.bind(sb.buf.p);
     hipStream_t s = e->stream;
     if (!keep) {
-        HIP_TRY(hipMemcpyAsync(base + o_ts, in->ts_ms, (size_t)n * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(base + o_cnt, in->count, (size_t)n * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(base + o_fl, in->flags, n, hipMemcpyHostToDevice, s));
-        if (in->entry_ref) HIP_TRY(hipMemcpyAsync(base + o_er, in->entry_ref, (size_t)n * 8, hipMemcpyHostToDevice, s));
-        if (in->create_ts) HIP_TRY(hipMemcpyAsync(base + o_ct, in->create_ts, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        SF_TRY(p.upload(h2d_on(s)));
         std::copy(key, key + 5, sb.key);
         std::copy(fp, fp + 3, sb.fp);
         sb.n = n;
@@ -1788,17 +1530,11 @@ static int stage_in_events(sf_engine* e, StageBuf& sb, const sf_event_batch* in,
         // final (the caller only appends), only the new ones are copied
         const uint32_t from = (keep && sb.st_src == status && sb.st_n <= n_status) ? sb.st_n : 0;
         if (n_status > from)
-            HIP_TRY(hipMemcpyAsync(base + o_st + from, status + from, n_status - from, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(*dstatus + from, status + from, n_status - from, hipMemcpyHostToDevice, s));
         sb.st_src = status; sb.st_n = n_status;
     } else {
         sb.st_src = nullptr; sb.st_n = 0;
     }
-    b = DevBatch{};
-    b.n = n;
-    b.ts = (const int64_t*)(base + o_ts); b.cnt = (const int32_t*)(base + o_cnt); b.flags = (const uint8_t*)(base + o_fl);
-    b.eref = in->entry_ref ? (const int64_t*)(base + o_er) : nullptr;
-    b.cts = in->create_ts ? (const int64_t*)(base + o_ct) : nullptr;
-    *dstatus = (uint8_t*)(base + o_st);
     return SF_OK;
 }
 
@@ -1816,18 +1552,18 @@ static int sx_exchange(sf_engine* e, sf_allgather_fn fn, void* ctx, const int64_
         if (r != ncclSuccess) return fail(SF_ERR_DEVICE, std::string("ncclAllGather: ") + ncclGetErrorString(r));
         return SF_OK;
     }
-    e->sx_hsend.resize(words);
-    e->sx_hrecv.resize(words * N);
-    HIP_TRY(hipMemcpyAsync(e->sx_hsend.data(), d_send, bytes, hipMemcpyDeviceToHost, s));
+    e->sx.hsend.resize(words);
+    e->sx.hrecv.resize(words * N);
+    HIP_TRY(hipMemcpyAsync(e->sx.hsend.data(), d_send, bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (fn(ctx, e->sx_hsend.data(), e->sx_hrecv.data(), bytes) != 0) return fail(SF_ERR_DEVICE, "all-gather callback failed");
+    if (fn(ctx, e->sx.hsend.data(), e->sx.hrecv.data(), bytes) != 0) return fail(SF_ERR_DEVICE, "all-gather callback failed");
     return SF_OK;                               // (every rank's message in sx_hrecv; the plan step reads it there)
 }
 
 static int sx_recv_reserve(sf_engine* e, size_t words) {
-    if (e->sx_recv.bytes >= words * 8) return SF_OK;
+    if (e->sx.recv.bytes >= words * 8) return SF_OK;
     HIP_TRY(hipStreamSynchronize(e->stream));
-    return e->sx_recv.reserve(e->pool, words * 8);
+    return e->sx.recv.reserve(e->pool, words * 8);
 }
 
 int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, sf_verdicts* out,
@@ -1843,13 +1579,13 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
     SF_TRY(drain(e));
     const uint32_t n = in->n, N = e->cfg.shard_count;
     hipStream_t s = e->stream;
-    if (!e->sx_msg) SF_TRY(e->pool.alloc(&e->sx_msg, SX_WORDS * 8));
-    if (wide && !e->sxw_msg) SF_TRY(e->pool.alloc(&e->sxw_msg, SXW_WORDS * 8));
-    if (wide && !e->sxw_segs) SF_TRY(e->pool.alloc(&e->sxw_segs, (size_t)SXW_MAX_SEGS * sizeof(SxwSeg)));
-    if (wide) e->sxw_hsegs.resize(SXW_MAX_SEGS);
+    if (!e->sx.msg) SF_TRY(e->pool.alloc(&e->sx.msg, SX_WORDS * 8));
+    if (wide && !e->sx.wmsg) SF_TRY(e->pool.alloc(&e->sx.wmsg, SXW_WORDS * 8));
+    if (wide && !e->sx.wsegs) SF_TRY(e->pool.alloc(&e->sx.wsegs, (size_t)SXW_MAX_SEGS * sizeof(SxwSeg)));
+    if (wide) e->sx.whsegs.resize(SXW_MAX_SEGS);
     const size_t mwords = wide ? SXW_WORDS : SX_WORDS;
-    int64_t* const msg = wide ? e->sxw_msg : e->sx_msg;    // the level messages (the header uses sx_msg)
-    if (!e->sx_ibuf) SF_TRY(e->pool.alloc(&e->sx_ibuf, e->cfg.max_batch));
+    int64_t* const msg = wide ? e->sx.wmsg : e->sx.msg;    // the level messages (the header uses sx_msg)
+    if (!e->sx.ibuf) SF_TRY(e->pool.alloc(&e->sx.ibuf, e->cfg.max_batch));
     SF_TRY(sys_buffers_ensure(e));
     SF_TRY(sx_recv_reserve(e, (size_t)N * mwords));
     const bool with_ox = in->origin || e->st.xmap;
@@ -1859,29 +1595,30 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
     Work& w = sl.w;
     DevBatch b{};
     DevVerdicts dv{};
-    SF_TRY(stage_batch(e, in, out, s, b, dv));
+    StagePlan vout(false, out->mem == SF_MEM_HOST);
+    SF_TRY(stage_batch(e, in, out, s, b, dv, vout));
     SF_TRY(auth_apply(e, sl, b, s));             // this rank's own events, before the exchange sees them
     const int64_t* dseq = seq;
     if (in->mem == SF_MEM_HOST && n) {
-        if (!e->sx_seq) SF_TRY(e->pool.alloc(&e->sx_seq, (size_t)e->cfg.max_batch * 8));
-        HIP_TRY(hipMemcpyAsync(e->sx_seq, seq, (size_t)n * 8, hipMemcpyHostToDevice, s));
-        dseq = e->sx_seq;
+        if (!e->sx.seq) SF_TRY(e->pool.alloc(&e->sx.seq, (size_t)e->cfg.max_batch * 8));
+        HIP_TRY(hipMemcpyAsync(e->sx.seq, seq, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        dseq = e->sx.seq;
     }
     HIP_TRY(hipMemsetAsync(w.err, 0, sizeof(int32_t), s));
     DevState stl = e->st;
     stl.err = w.err;
     SxArgs a{};
-    a.b = b; a.seq = dseq; a.msg = e->sx_msg; a.vstatus = dv.status;
+    a.b = b; a.seq = dseq; a.msg = e->sx.msg; a.vstatus = dv.status;
     a.r = e->sys; a.S = stl.S; a.wl = stl.wl; a.interval = stl.interval; a.max_rt = stl.max_rt;
     a.interval_sec = stl.interval / 1000.0; a.st = stl;
-    a.ibuf = e->st.n_prule ? e->sx_ibuf : nullptr;
+    a.ibuf = e->st.n_prule ? e->sx.ibuf : nullptr;
     a.g = std::__gcd((int64_t)stl.wl, (int64_t)1000);
     // every rank's message on the host: the plan step runs there (one sync per level)
     auto gather = [&](const int64_t* d_send, size_t words, std::vector<int64_t>& h) -> int {
-        SF_TRY(sx_exchange(e, allgather, ctx, d_send, (int64_t*)e->sx_recv.p, words));
-        if (allgather) { h.assign(e->sx_hrecv.begin(), e->sx_hrecv.begin() + words * N); return SF_OK; }
+        SF_TRY(sx_exchange(e, allgather, ctx, d_send, (int64_t*)e->sx.recv.p, words));
+        if (allgather) { h.assign(e->sx.hrecv.begin(), e->sx.hrecv.begin() + words * N); return SF_OK; }
         h.resize(words * N);
-        HIP_TRY(hipMemcpyAsync(h.data(), e->sx_recv.p, words * N * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h.data(), e->sx.recv.p, words * N * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         return SF_OK;
     };
@@ -1890,8 +1627,8 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
     bool neg = false;
     std::vector<int64_t> h;
     {
-        HIP_TRY(sx_header(a, e->sx_msg, s));
-        SF_TRY(gather(e->sx_msg, 5, h));
+        HIP_TRY(sx_header(a, e->sx.msg, s));
+        SF_TRY(gather(e->sx.msg, 5, h));
         for (uint32_t k = 0; k < N; k++) {
             const int64_t* x = &h[(size_t)k * 5];
             if (!x[4]) continue;
@@ -1926,7 +1663,7 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
     EntryNode enh;
     HIP_TRY(hipMemcpyAsync(&enh, e->en, sizeof enh, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    uint32_t* d_lq = (uint32_t*)e->sx_recv.p;     // (sx_locate's result: the recv buffer is free then)
+    uint32_t* d_lq = (uint32_t*)e->sx.recv.p;     // (sx_locate's result: the recv buffer is free then)
     // ---- rounds
     a.msg = msg;
     HIP_TRY(wide ? sxw_nodelta(msg, s) : sx_nodelta(msg, s));
@@ -1969,7 +1706,7 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
                 hp.P = hw.base.P;
             }
             if (wide) {
-                sxw_reduce(h.data(), (int)N, &hw, e->sxw_hsegs.data(), a.r, a.S, a.interval_sec);
+                sxw_reduce(h.data(), (int)N, &hw, e->sx.whsegs.data(), a.r, a.S, a.interval_sec);
                 hp.q = hw.q; hp.done = hw.done;
             } else {
                 sx_reduce(h.data(), (int)N, &hp, a.r, a.interval_sec);
@@ -1992,9 +1729,9 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
         if (lq < lp || lq > n) return fail(SF_ERR_DEVICE, "exchange plan: bad local range");
         if (lq > lp) {
             if (wide && hw.nseg)
-                HIP_TRY(hipMemcpyAsync(e->sxw_segs, e->sxw_hsegs.data(), (size_t)hw.nseg * sizeof(SxwSeg),
+                HIP_TRY(hipMemcpyAsync(e->sx.wsegs, e->sx.whsegs.data(), (size_t)hw.nseg * sizeof(SxwSeg),
                                        hipMemcpyHostToDevice, s));
-            hipError_t le = wide ? sxw_mask(a, e->sys_mask, lp, lq, e->sxw_segs, hw.nseg, s)
+            hipError_t le = wide ? sxw_mask(a, e->sys_mask, lp, lq, e->sx.wsegs, hw.nseg, s)
                                  : sx_mask(a, e->sys_mask, lp, lq, hp.P, s);
             if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("exchange mask: ") + hipGetErrorString(le));
             DevBatch v;
@@ -2026,7 +1763,7 @@ int sf_submit_node(sf_engine* e, const sf_event_batch* in, const int64_t* seq, s
     HIP_TRY(hipStreamSynchronize(s));
     e->stats.sys_rounds += rounds;
     e->stats.sys_exchanges += levels;
-    return finish_sync(e, sl, out, dv, n, false);
+    return finish_sync(e, sl, vout, n, false);
 }
 
 int sf_system_plan(sf_engine* e, const sf_event_batch* in, const uint8_t* status, uint32_t p, uint32_t* q,
@@ -2221,902 +1958,6 @@ int sf_read_rule_states(sf_engine* e, uint32_t first, uint32_t n, sf_rule_state*
     return SF_OK;
 }
 
-int sf_snapshot(sf_engine* e, int64_t now_ms, sf_metric_row* out, uint32_t cap, uint32_t* n_out) {
-    if (!e || !n_out || (cap && !out)) return fail(SF_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    SF_TRY(en_fence(e));
-    *n_out = 0;
-    hipStream_t s = e->stream;
-    if (!e->snap_ready) {
-        const int rc = [&]() -> int {
-            SF_TRY(e->pool.alloc(&e->snap_counts, (size_t)e->R * 4));
-            SF_TRY(e->pool.alloc(&e->snap_offsets, (size_t)e->R * 4));
-            SF_TRY(e->pool.alloc(&e->snap_total, 4));
-            HIP_TRY(rocprim_scan_bytes(e->R, &e->snap_scan_bytes));
-            return e->pool.alloc(&e->snap_scan, min16(e->snap_scan_bytes));
-        }();
-        if (rc) { e->pool.release_all(e->snap_counts, e->snap_offsets, e->snap_total, e->snap_scan); return rc; }
-        e->snap_ready = true;
-    }
-    SF_TRY(e->snap_rows.reserve(e->pool, (size_t)cap * sizeof(sf_metric_row)));
-    sf_metric_row* rows = (sf_metric_row*)e->snap_rows.p;
-    HIP_TRY(launch_snapshot(e->st, now_ms, e->cfg.shard_count, e->cfg.shard_index, e->snap_counts, e->snap_offsets,
-                            rows, cap, e->snap_total, e->snap_scan, e->snap_scan_bytes, s));
-    uint32_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, e->snap_total, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const uint32_t k = std::min(total, cap);
-    if (k) HIP_TRY(hipMemcpy(out, rows, (size_t)k * sizeof(sf_metric_row), hipMemcpyDeviceToHost));
-    *n_out = total;
-    return total <= cap ? SF_OK : fail(SF_ERR_CAPACITY, "snapshot rows exceed cap");
-}
-// ---------------------------------------------------------------- metrics.log
-int sf_load_resource_names(sf_engine* e, const char* bytes, const uint64_t* offsets, const int32_t* types,
-                           uint32_t n) {
-    if (!e || (n && (!offsets || (!bytes && offsets[n])))) return fail(SF_ERR_INVALID, "null argument");
-    for (uint32_t i = 0; i < n; i++)
-        if (offsets[i + 1] < offsets[i]) return fail(SF_ERR_INVALID, "name offsets must be non-decreasing");
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->pool.release_all(e->nm_bytes, e->nm_off, e->nm_types);
-    e->n_names = 0;
-    const uint64_t nb = n ? offsets[n] - offsets[0] : 0;
-    SF_TRY(e->pool.alloc(&e->nm_bytes, min16(nb)));
-    SF_TRY(e->pool.alloc(&e->nm_off, ((size_t)n + 1) * 8));
-    if (nb) HIP_TRY(hipMemcpy(e->nm_bytes, bytes + offsets[0], nb, hipMemcpyHostToDevice));
-    std::vector<uint64_t> off(offsets, offsets + n + 1);
-    for (auto& o : off) o -= offsets[0];
-    HIP_TRY(hipMemcpy(e->nm_off, off.data(), off.size() * 8, hipMemcpyHostToDevice));
-    if (types) {
-        SF_TRY(e->pool.alloc(&e->nm_types, min16((size_t)n * 4)));
-        if (n) HIP_TRY(hipMemcpy(e->nm_types, types, (size_t)n * 4, hipMemcpyHostToDevice));
-    }
-    e->n_names = n;
-    return SF_OK;
-}
-
-// The metric log's buffers: the per-node ones and the events on first use,
-// the per-row ones for `rows` rows, the scan / sort scratch for both.  A
-// failure anywhere leaves none (ml_pool cleared), and the next call starts over.
-static int ml_build(sf_engine* e, uint32_t rows) {
-    auto& ml = e->ml;
-    DevPool& m = e->ml_pool;
-    const uint32_t nodes = e->R + 1;
-    if (!ml.ready) {
-        SF_TRY(m.alloc(&ml.mask, (size_t)nodes * 8));
-        SF_TRY(m.alloc(&ml.counts, (size_t)nodes * 4));
-        SF_TRY(m.alloc(&ml.offsets, (size_t)nodes * 4));
-        SF_TRY(m.alloc(&ml.total, 4));
-        SF_TRY(m.alloc(&ml.bytes, 8));
-        for (auto& x : e->ml_ev) if (!x) HIP_TRY(hipEventCreate(&x));
-        ml.ready = true;
-    }
-    if (rows > ml.row_cap || !ml.row_cap) {
-        const uint32_t cap = std::max<uint32_t>(rows, 1024);
-        m.release_all(ml.rows, ml.keys, ml.order, ml.len, ml.off);
-        ml.row_cap = 0;
-        SF_TRY(m.alloc(&ml.rows, (size_t)cap * sizeof(sf_metric_row)));
-        SF_TRY(m.alloc(&ml.keys, (size_t)cap * 2));
-        SF_TRY(m.alloc(&ml.order, (size_t)cap * 8));
-        SF_TRY(m.alloc(&ml.len, (size_t)cap * 8));
-        SF_TRY(m.alloc(&ml.off, (size_t)cap * 8));
-        ml.row_cap = cap;
-    }
-    size_t tb = 0;
-    HIP_TRY(mlog_temp_bytes(nodes, ml.row_cap, &tb));
-    return ml.tmp.reserve(m, tb);
-}
-static int ml_reserve(sf_engine* e, uint32_t rows) {
-    const int rc = ml_build(e, rows);
-    if (rc) { e->ml_pool.clear(); e->ml = {}; }
-    return rc;
-}
-
-// line lengths -> offsets -> lines, copied to the caller's host buffer
-static int ml_format(sf_engine* e, const uint32_t* order, uint32_t n, int64_t tz, char* out, uint64_t cap,
-                     uint64_t* len_out) {
-    hipStream_t s = e->stream;
-    HIP_TRY(launch_fmt_len(e->ml.rows, order, n, e->nm_bytes, e->nm_off, e->nm_types, e->n_names, tz, e->ml.len,
-                           e->ml.off, e->ml.bytes, e->ml.tmp.p, e->ml.tmp.bytes, s));
-    uint64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, e->ml.bytes, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    *len_out = total;
-    if (total > cap) return fail(SF_ERR_CAPACITY, "metric log bytes exceed cap");
-    SF_TRY(e->ml.out.reserve(e->ml_pool, total));
-    HIP_TRY(launch_fmt_write(e->ml.rows, order, n, e->nm_bytes, e->nm_off, e->nm_types, e->n_names, tz, e->ml.off,
-                             (char*)e->ml.out.p, s));
-    HIP_TRY(hipEventRecord(e->ml_ev[2], s));
-    if (total) HIP_TRY(hipMemcpyAsync(out, e->ml.out.p, total, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return SF_OK;
-}
-
-int sf_metric_log(sf_engine* e, int64_t now_ms, int64_t tz_offset_ms, int include_entry_node, char* out,
-                  uint64_t cap, uint64_t* len_out, uint32_t* n_lines) {
-    if (!e || !len_out || (cap && !out)) return fail(SF_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    SF_TRY(en_fence(e));
-    *len_out = 0;
-    if (n_lines) *n_lines = 0;
-    SF_TRY(ml_reserve(e, 0));
-    hipStream_t s = e->stream;
-    const bool with_en = include_entry_node != 0;
-    const uint32_t nodes = e->R + (with_en ? 1u : 0u);
-    // the ENTRY_NODE line: this engine's node, or the one set by sf_set_report_entry_node
-    // (its windows; lastFetchTime stays this engine's, MetricTimerListener.java:40-69)
-    EntryNode* en = e->en;
-    if (with_en && e->report_set) {
-        if (!e->en_report) SF_TRY(e->pool.alloc(&e->en_report, sizeof(EntryNode)));
-        HIP_TRY(hipMemcpyAsync(e->en_report, &e->report, sizeof(EntryNode), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(&e->en_report->last_fetch, &e->en->last_fetch, 8, hipMemcpyDeviceToDevice, s));
-        en = e->en_report;
-    }
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)nodes + 3) / 4, (uint64_t)cus * 16);
-    HIP_TRY(hipEventRecord(e->ml_ev[0], s));
-    HIP_TRY(launch_mlog_count(e->st, en, with_en, e->cfg.shard_count, e->cfg.shard_index, now_ms, e->ml.mask,
-                              e->ml.counts, e->ml.offsets, e->ml.total, e->ml.tmp.p, e->ml.tmp.bytes, grid, e->ml_ev[1], s));
-    uint32_t rows = 0;
-    HIP_TRY(hipMemcpyAsync(&rows, e->ml.total, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    SF_TRY(ml_reserve(e, rows));
-    uint32_t* ord = e->ml.order;
-    HIP_TRY(launch_mlog_rows(e->st, en, with_en, e->cfg.shard_count, e->cfg.shard_index, now_ms, e->ml.mask,
-                             e->ml.offsets, rows, e->ml.rows, e->ml.keys, e->ml.keys + e->ml.row_cap, ord,
-                             ord + e->ml.row_cap, e->ml.tmp.p, e->ml.tmp.bytes, grid, s));
-    if (n_lines) *n_lines = rows;
-    if (en != e->en) HIP_TRY(hipMemcpyAsync(&e->en->last_fetch, &en->last_fetch, 8, hipMemcpyDeviceToDevice, s));
-    SF_TRY(ml_format(e, ord + e->ml.row_cap, rows, tz_offset_ms, out, cap, len_out));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, e->ml_ev[0], e->ml_ev[1]) == hipSuccess) e->stats.metric_scan_ms = ms;
-    if (hipEventElapsedTime(&ms, e->ml_ev[0], e->ml_ev[2]) == hipSuccess) e->stats.metric_log_ms = ms;
-    return SF_OK;
-}
-
-int sf_format_metric_rows(sf_engine* e, const sf_metric_row* rows, uint32_t n, int64_t tz_offset_ms, char* out,
-                          uint64_t cap, uint64_t* len_out) {
-    if (!e || !len_out || (n && !rows) || (cap && !out)) return fail(SF_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    *len_out = 0;
-    SF_TRY(ml_reserve(e, n));
-    if (n) HIP_TRY(hipMemcpyAsync(e->ml.rows, rows, (size_t)n * sizeof(sf_metric_row), hipMemcpyHostToDevice,
-                                  e->stream));
-    return ml_format(e, nullptr, n, tz_offset_ms, out, cap, len_out);
-}
-// ---------------------------------------------------------------- cluster token server
-// Owner shard of a cluster rule's requests (sentinel_flow.h, sf_token_shard):
-// a namespace with a GlobalRequestLimiter is one sequential gate, so all its
-// rules live on namespace_id % N; any other rule on flow_id % N.
-static uint32_t tok_rule_owner(int64_t flow_id, uint32_t ns_id, const std::vector<sf_namespace>& ns, uint32_t N) {
-    for (const sf_namespace& x : ns)
-        if (x.namespace_id == ns_id) {
-            if (x.max_allowed_qps >= 0) return ns_id % N;
-            break;
-        }
-    return flow_id <= 0 ? 0u : (uint32_t)((uint64_t)flow_id % N);
-}
-
-// Rebuild the device rule table, flowId index and namespace table from the
-// host copies (ClusterFlowRuleManager / ClusterParamFlowRuleManager /
-// ClusterServerConfigManager state).  Metric state is reset when
-// `reset_state` (a rule reload creates new ClusterMetric objects:
-// ClusterFlowRuleManager.java:361-362, ClusterParamFlowRuleManager.java:354-355).
-static int tok_rebuild(sf_engine* e, bool reset_state) {
-    TokState& ts = e->ts;
-    const uint32_t nf = (uint32_t)e->host_cflow.size(), np = (uint32_t)e->host_cparam.size();
-    std::unordered_map<uint32_t, int32_t> ns_index;
-    for (size_t i = 0; i < e->host_ns.size(); i++) ns_index.emplace(e->host_ns[i].namespace_id, (int32_t)i);
-    std::vector<ClRule> rules(nf + np);
-    auto fill = [&](ClRule& r, int64_t id, double count, int32_t tt, uint32_t ns, int32_t S, int32_t I) {
-        r.count = count; r.flow_id = id; r.threshold_type = tt;
-        auto it = ns_index.find(ns);
-        r.ns = it == ns_index.end() ? -1 : it->second;
-        r.S = S; r.wl = I / S; r.interval = I;
-    };
-    const uint32_t N = e->cfg.shard_count;
-    for (uint32_t i = 0; i < nf; i++) {
-        const sf_cluster_flow_rule& f = e->host_cflow[i];
-        fill(rules[i], f.flow_id, f.count, f.threshold_type, f.namespace_id, f.sample_count, f.window_interval_ms);
-        rules[i].is_param = 0; rules[i].item_off = rules[i].item_cnt = 0;
-        rules[i].owner = tok_rule_owner(f.flow_id, f.namespace_id, e->host_ns, N);
-    }
-    for (uint32_t i = 0; i < np; i++) {
-        const sf_cluster_param_rule& f = e->host_cparam[i];
-        ClRule& r = rules[nf + i];
-        fill(r, f.flow_id, f.count, f.threshold_type, f.namespace_id, f.sample_count, f.window_interval_ms);
-        r.is_param = 1; r.item_off = f.item_offset; r.item_cnt = f.item_count;
-        r.owner = tok_rule_owner(f.flow_id, f.namespace_id, e->host_ns, N);
-    }
-    // flowId -> rule index, open addressing; the first rule of an id wins (like the oracle's lookup)
-    uint64_t cap = 16;
-    while (cap < 2ull * (nf + np) + 2) cap <<= 1;
-    std::vector<IdSlot> tab(cap, IdSlot{0, -1, -1});
-    auto put = [&](int64_t id, int32_t idx, bool param) {
-        uint64_t x = (uint64_t)id * 0x9e3779b97f4a7c15ULL;
-        uint64_t i = mix64(x) & (cap - 1);
-        while (tab[i].id != 0 && tab[i].id != id) i = (i + 1) & (cap - 1);
-        tab[i].id = id;
-        int32_t& slot = param ? tab[i].param : tab[i].flow;
-        if (slot < 0) slot = idx;
-    };
-    for (uint32_t i = 0; i < nf; i++) if (rules[i].flow_id > 0) put(rules[i].flow_id, (int32_t)i, false);
-    for (uint32_t i = 0; i < np; i++) if (rules[nf + i].flow_id > 0) put(rules[nf + i].flow_id, (int32_t)(nf + i), true);
-    std::vector<ClNs> ns(e->host_ns.size());
-    for (size_t i = 0; i < ns.size(); i++) {
-        ns[i].connected = e->host_ns[i].connected_count;
-        ns[i].has_limiter = e->host_ns[i].max_allowed_qps >= 0;   // GlobalRequestLimiter.initIfAbsent
-        ns[i].max_qps = e->host_ns[i].max_allowed_qps;
-    }
-    std::vector<DevHotItem> items(e->host_citems.size());
-    for (size_t i = 0; i < items.size(); i++) {
-        items[i].bits = e->host_citems[i].bits; items[i].count = e->host_citems[i].count; items[i].tag = e->host_citems[i].tag;
-    }
-    hipStream_t s = e->stream;
-    auto upload = [&](void** dst, const void* src, size_t bytes) -> int {
-        e->pool.release(*dst);
-        SF_TRY(e->pool.alloc(dst, min16(bytes)));
-        if (bytes) HIP_TRY(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, s));
-        return SF_OK;
-    };
-    SF_TRY(upload((void**)&ts.rules, rules.data(), rules.size() * sizeof(ClRule)));
-    SF_TRY(upload((void**)&ts.idtab, tab.data(), tab.size() * sizeof(IdSlot)));
-    SF_TRY(upload((void**)&ts.ns, ns.data(), ns.size() * sizeof(ClNs)));
-    SF_TRY(upload((void**)&ts.items, items.data(), items.size() * sizeof(DevHotItem)));
-    e->pool.release(ts.rmulti);
-    SF_TRY(e->pool.alloc(&ts.rmulti, min16(rules.size())));   // per-call multi-value flags
-    ts.id_mask = cap - 1;
-    ts.n_flow = nf; ts.n_rules = nf + np; ts.n_ns = (uint32_t)ns.size();
-    if (reset_state) {
-        e->pool.release(ts.fstate);
-        SF_TRY(e->pool.alloc(&ts.fstate, std::max<size_t>(nf, 1) * sizeof(ClFlowState)));
-        HIP_TRY(tok_init_flow_state(ts.fstate, nf, s));
-        if (!ts.cptab) {
-            uint64_t pc = 1024;
-            while (pc < std::max<uint64_t>(e->cfg.param_capacity, 1024)) pc <<= 1;
-            SF_TRY(e->pool.alloc(&ts.cptab, pc * sizeof(CpSlot)));
-            ts.cp_mask = pc - 1;
-        }
-        HIP_TRY(hipMemsetAsync(ts.cptab, 0, (ts.cp_mask + 1) * sizeof(CpSlot), s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    return SF_OK;
-}
-
-// Per-flow-rule tables of the concurrency tokens: the two time-outs (always
-// rebuilt) and nowCalls (replaced by `now` if given, created zeroed if absent).
-static int cc_tables(sf_engine* e, const std::vector<int32_t>* now) {
-    CcState& cs = e->cc.cs;
-    const size_t nf = e->host_cflow.size(), m = std::max<size_t>(nf, 1);
-    std::unordered_map<int64_t, const sf_concurrent_config*> by_id;
-    for (const sf_concurrent_config& c : e->cc.cfg) by_id.emplace(c.flow_id, &c);
-    std::vector<CcCfg> cfg(m, CcCfg{CC_DEFAULT_TIMEOUT, CC_DEFAULT_TIMEOUT});
-    for (size_t i = 0; i < nf; i++) {
-        auto it = by_id.find(e->host_cflow[i].flow_id);
-        if (it != by_id.end()) cfg[i] = CcCfg{it->second->resource_timeout_ms, it->second->client_offline_time_ms};
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->pool.release(cs.cfg);
-    SF_TRY(e->pool.alloc(&cs.cfg, m * sizeof(CcCfg)));
-    HIP_TRY(hipMemcpy((void*)cs.cfg, cfg.data(), m * sizeof(CcCfg), hipMemcpyHostToDevice));
-    if (now || !cs.now) {
-        e->pool.release(cs.now);
-        SF_TRY(e->pool.alloc(&cs.now, m * 4));
-        if (now) HIP_TRY(hipMemcpy(cs.now, now->data(), m * 4, hipMemcpyHostToDevice));
-        else HIP_TRY(hipMemset(cs.now, 0, m * 4));
-    }
-    if (!cs.ctr) {
-        SF_TRY(e->pool.alloc(&cs.ctr, sizeof(CcCounters)));
-        HIP_TRY(hipMemset(cs.ctr, 0, sizeof(CcCounters)));
-    }
-    return SF_OK;
-}
-
-int sf_load_namespaces(sf_engine* e, const sf_namespace* ns, uint32_t n) {
-    if (!e || (n && !ns)) return fail(SF_ERR_INVALID, "null argument");
-    if (n > 255) return fail(SF_ERR_UNSUPPORTED, "at most 255 namespaces");
-    std::lock_guard<std::mutex> lk(e->mu);
-    e->host_ns.assign(ns, ns + n);
-    // GlobalRequestLimiter state of the loaded namespaces starts empty
-    LimState z;
-    for (int k = 0; k < LIM_S; k++) { z.ws[k] = WS_NONE; z.v[k] = 0; }
-    std::vector<LimState> lim(std::max<uint32_t>(n, 1), z);
-    e->pool.release(e->ts.lim);
-    SF_TRY(e->pool.alloc(&e->ts.lim, lim.size() * sizeof(LimState)));
-    HIP_TRY(hipMemcpyAsync(e->ts.lim, lim.data(), lim.size() * sizeof(LimState), hipMemcpyHostToDevice, e->stream));
-    return tok_rebuild(e, false);
-}
-
-int sf_load_cluster_rules(sf_engine* e, const sf_cluster_flow_rule* flow, uint32_t n_flow,
-                          const sf_cluster_param_rule* param, uint32_t n_param, const sf_hot_item* items,
-                          uint32_t n_items) {
-    if (!e || (n_flow && !flow) || (n_param && !param) || (n_items && !items)) return fail(SF_ERR_INVALID, "null argument");
-    auto check = [&](int32_t S, int32_t I) {
-        return S > 0 && S <= CL_MAXS && I > 0 && I % S == 0;   // LeapArray.java:70-87
-    };
-    for (uint32_t i = 0; i < n_flow; i++)
-        if (!check(flow[i].sample_count, flow[i].window_interval_ms))
-            return fail(SF_ERR_UNSUPPORTED, "cluster flow rule: sample_count must be 1..16 and divide window_interval_ms");
-    for (uint32_t i = 0; i < n_param; i++) {
-        if (!check(param[i].sample_count, param[i].window_interval_ms))
-            return fail(SF_ERR_UNSUPPORTED, "cluster param rule: sample_count must be 1..16 and divide window_interval_ms");
-        if ((uint64_t)param[i].item_offset + param[i].item_count > n_items) return fail(SF_ERR_INVALID, "hot item range");
-    }
-    std::lock_guard<std::mutex> lk(e->mu);
-    // nowCalls of a flowId that stays loaded is kept (ClusterFlowRuleManager.java:271-375)
-    std::unordered_map<int64_t, int32_t> kept;
-    if (e->cc.cs.now && !e->host_cflow.empty()) {
-        std::vector<int32_t> old(e->host_cflow.size());
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipMemcpy(old.data(), e->cc.cs.now, old.size() * 4, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < old.size(); i++)
-            if (e->host_cflow[i].flow_id > 0) kept.emplace(e->host_cflow[i].flow_id, old[i]);
-    }
-    e->host_cflow.assign(flow, flow + n_flow);
-    e->host_cparam.assign(param, param + n_param);
-    e->host_citems.assign(items, items + n_items);
-    int rc = tok_rebuild(e, true);
-    if (rc || !e->cc.cs.now) return rc;
-    std::vector<int32_t> now(std::max<uint32_t>(n_flow, 1), 0);
-    for (uint32_t i = 0; i < n_flow; i++) {                    // (the first rule of an id is the one looked up)
-        auto it = kept.find(flow[i].flow_id);
-        if (it != kept.end()) { now[i] = it->second; kept.erase(it); }
-    }
-    return cc_tables(e, &now);
-}
-
-// the scratch sizes of the work sets (sf_worksets.h) as rocPRIM states them
-static int tok_temp_query(uint32_t n, size_t* s8, size_t* s64, size_t* scan) { HIP_TRY(tok_query_temp(n, s8, s64, scan)); return SF_OK; }
-static int cc_temp_query(uint32_t n, size_t* bytes) { HIP_TRY(cc_query_temp(n, bytes)); return SF_OK; }
-static int dg_temp_query(uint32_t n, uint32_t key_bits, size_t* bytes) { HIP_TRY(dg_sort_bytes(n, key_bits, bytes)); return SF_OK; }
-
-// token state present (rules built, namespace limiter allocated); caller holds e->mu
-static int tok_ready(sf_engine* e) {
-    if (!e->ts.rules) SF_TRY(tok_rebuild(e, true));
-    if (!e->ts.lim) {
-        LimState z; for (int k = 0; k < LIM_S; k++) { z.ws[k] = WS_NONE; z.v[k] = 0; }
-        SF_TRY(e->pool.alloc(&e->ts.lim, sizeof(LimState)));
-        HIP_TRY(hipMemcpy(e->ts.lim, &z, sizeof z, hipMemcpyHostToDevice));
-    }
-    return SF_OK;
-}
-
-int sf_request_tokens(sf_engine* e, const sf_token_batch* in, sf_token_results* out) {
-    if (!e || !in || !out || !out->status) return fail(SF_ERR_INVALID, "null argument");
-    if (in->n == 0) return SF_OK;
-    if (!in->flow_id || !in->count || !in->flags || !in->ts_ms) return fail(SF_ERR_INVALID, "missing request array");
-    if ((in->param_tag == nullptr) != (in->param_bits == nullptr)) return fail(SF_ERR_INVALID, "param_tag/param_bits");
-    std::lock_guard<std::mutex> lk(e->mu);
-    const uint32_t n = in->n;
-    SF_TRY(tok_work_ensure(e->tw, n, e->cfg.max_batch, tok_temp_query));
-    SF_TRY(tok_ready(e));
-    hipStream_t s = e->stream;
-    TokBatch b{};
-    b.n = n;
-    const bool has_param = in->param_tag != nullptr;
-    // Collection params: the value arrays hold param_off[n] elements
-    uint32_t n_vals = n;
-    if (in->param_off) {
-        if (in->mem == SF_MEM_HOST) n_vals = in->param_off[n];
-        else HIP_TRY(hipMemcpy(&n_vals, in->param_off + n, 4, hipMemcpyDeviceToHost));
-    }
-    // staging: inputs then outputs, 256-B aligned
-    Layout L;
-    const size_t off_fid = L.take((size_t)n * 8), off_cnt = L.take((size_t)n * 4), off_fl = L.take(n), off_ts = L.take((size_t)n * 8);
-    const size_t off_tag = L.take_if(has_param, n_vals), off_bits = L.take_if(has_param, (size_t)n_vals * 8);
-    const size_t off_po = L.take_if(in->param_off, ((size_t)n + 1) * 4);
-    const size_t off_st = L.take(n), off_rem = L.take((size_t)n * 4), off_wt = L.take((size_t)n * 4);
-    SF_TRY(e->tok_stage.reserve(e->pool, L.size()));
-    char* base = e->tok_stage.at(0);
-    if (in->mem == SF_MEM_HOST) {
-        HIP_TRY(hipMemcpyAsync(base + off_fid, in->flow_id, (size_t)n * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(base + off_cnt, in->count, (size_t)n * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(base + off_fl, in->flags, n, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(base + off_ts, in->ts_ms, (size_t)n * 8, hipMemcpyHostToDevice, s));
-        if (has_param && n_vals) {
-            HIP_TRY(hipMemcpyAsync(base + off_tag, in->param_tag, n_vals, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(base + off_bits, in->param_bits, (size_t)n_vals * 8, hipMemcpyHostToDevice, s));
-        }
-        if (in->param_off)
-            HIP_TRY(hipMemcpyAsync(base + off_po, in->param_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, s));
-        b.flow_id = (const int64_t*)(base + off_fid); b.count = (const int32_t*)(base + off_cnt);
-        b.flags = (const uint8_t*)(base + off_fl); b.ts = (const int64_t*)(base + off_ts);
-        b.ptag = has_param ? (const uint8_t*)(base + off_tag) : nullptr;
-        b.pbits = has_param ? (const uint64_t*)(base + off_bits) : nullptr;
-        b.poff = in->param_off ? (const uint32_t*)(base + off_po) : nullptr;
-    } else {
-        b.flow_id = in->flow_id; b.count = in->count; b.flags = in->flags; b.ts = in->ts_ms;
-        b.ptag = in->param_tag; b.pbits = in->param_bits; b.poff = in->param_off;
-    }
-    TokOut o{};
-    const bool host_out = out->mem == SF_MEM_HOST;
-    if (host_out) {
-        o.status = (int8_t*)(base + off_st); o.remaining = (int32_t*)(base + off_rem); o.wait = (int32_t*)(base + off_wt);
-    } else {
-        if (!out->remaining || !out->wait_ms) return fail(SF_ERR_INVALID, "device results need remaining and wait_ms");
-        o.status = out->status; o.remaining = out->remaining; o.wait = out->wait_ms;
-    }
-    HIP_TRY(hipMemsetAsync(e->st.err, 0, sizeof(int32_t), s));
-    hipError_t le = tok_launch(e->ts, e->tw.w, b, o, s);
-    if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("token launch: ") + hipGetErrorString(le));
-    if (host_out) {
-        HIP_TRY(hipMemcpyAsync(out->status, o.status, n, hipMemcpyDeviceToHost, s));
-        if (out->remaining) HIP_TRY(hipMemcpyAsync(out->remaining, o.remaining, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        if (out->wait_ms) HIP_TRY(hipMemcpyAsync(out->wait_ms, o.wait, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    }
-    int32_t err = 0;
-    HIP_TRY(hipMemcpyAsync(&err, e->st.err, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (err) return fail(err, err == SF_ERR_CAPACITY ? "cluster param table capacity exceeded"
-                                                     : "invalid token batch (a request owned by another shard?)");
-    return SF_OK;
-}
-
-int sf_token_shard(const sf_cluster_flow_rule* flow, uint32_t n_flow, const sf_cluster_param_rule* param,
-                   uint32_t n_param, const sf_namespace* ns, uint32_t n_ns, uint32_t shard_count,
-                   const int64_t* flow_id, const uint8_t* flags, uint32_t n, uint32_t* out_shard) {
-    if ((n_flow && !flow) || (n_param && !param) || (n_ns && !ns) || (n && (!flow_id || !flags || !out_shard)) ||
-        shard_count == 0)
-        return fail(SF_ERR_INVALID, "sf_token_shard arguments");
-    const std::vector<sf_namespace> nsv(ns, ns + n_ns);
-    std::unordered_map<int64_t, uint32_t> fo, po;                  // first rule of an id (tok_rebuild's lookup)
-    for (uint32_t i = 0; i < n_flow; i++)
-        if (flow[i].flow_id > 0) fo.emplace(flow[i].flow_id, tok_rule_owner(flow[i].flow_id, flow[i].namespace_id, nsv, shard_count));
-    for (uint32_t i = 0; i < n_param; i++)
-        if (param[i].flow_id > 0) po.emplace(param[i].flow_id, tok_rule_owner(param[i].flow_id, param[i].namespace_id, nsv, shard_count));
-    for (uint32_t i = 0; i < n; i++) {
-        const int64_t id = flow_id[i];
-        if (id <= 0) { out_shard[i] = 0; continue; }
-        const auto& m = (flags[i] & SF_TOK_PARAM) ? po : fo;
-        const auto it = m.find(id);
-        out_shard[i] = it != m.end() ? it->second : (uint32_t)((uint64_t)id % shard_count);
-    }
-    return SF_OK;
-}
-
-uint64_t sf_string_key(const uint8_t* bytes, uint32_t len) {   // FNV-1a 64 (the wire path's String key)
-    uint64_t h = 0xcbf29ce484222325ULL;
-    for (uint32_t i = 0; i < len; i++) { h ^= bytes[i]; h *= 0x100000001b3ULL; }
-    return h;
-}
-
-int sf_serve_frames(sf_engine* e, const sf_wire_batch* in, sf_wire_out* out) {
-    if (!e || !in || !out || !in->stream_off || !out->resp_off || !out->consumed || !out->stop)
-        return fail(SF_ERR_INVALID, "null argument");
-    if (in->n_streams == 0) return fail(SF_ERR_INVALID, "n_streams must be > 0");
-    if (e->cfg.shard_count > 1)
-        return fail(SF_ERR_UNSUPPORTED, "sf_serve_frames on a sharded token server: route decoded requests with sf_token_shard");
-    const uint32_t S = in->n_streams;
-    std::vector<uint64_t> soff(S + 1);
-    if (in->mem == SF_MEM_HOST) std::memcpy(soff.data(), in->stream_off, (S + 1) * sizeof(uint64_t));
-    else HIP_TRY(hipMemcpy(soff.data(), in->stream_off, (S + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    for (uint32_t s = 0; s < S; s++)
-        if (soff[s + 1] < soff[s]) return fail(SF_ERR_INVALID, "stream_off must be non-decreasing");
-    if (soff[S] >= (1ull << 31)) return fail(SF_ERR_CAPACITY, "wire batch must be < 2^31 bytes");
-    if (soff[S] && !in->bytes) return fail(SF_ERR_INVALID, "null bytes");
-    std::lock_guard<std::mutex> lk(e->mu);
-    out->n_frames = out->n_requests = out->n_responses = 0;
-    const uint32_t n = (uint32_t)soff[S];
-    if (soff[0] == n) {                          // nothing to read: every stream handled, no response
-        for (uint32_t s = 0; s < S; s++) { out->consumed[s] = 0; out->stop[s] = SF_WIRE_DONE; }
-        for (uint32_t s = 0; s <= S; s++) out->resp_off[s] = 0;
-        return SF_OK;
-    }
-    SF_TRY(tok_ready(e));
-    hipStream_t st = e->stream;
-    WireBufs w{};
-    w.n = n; w.S = S;
-    w.n_tiles = (n + WIRE_TILE - 1) / WIRE_TILE;
-    const uint32_t F = n / 2 + 1;                 // frames are >= 2 bytes
-    size_t tmp = 0;
-    { hipError_t qe = wire_query_temp(w.n_tiles, S, F, &tmp);
-      if (qe != hipSuccess) return fail(SF_ERR_DEVICE, std::string("wire temp: ") + hipGetErrorString(qe)); }
-    // one grow-only arena, 256-B aligned pieces
-    Layout L;
-    auto take = [&](size_t bytes) { return L.take(min16(bytes)); };
-    const bool host_in = in->mem == SF_MEM_HOST;
-    const size_t o_bytes = host_in ? take(n + 16) : 0, o_soff = host_in ? take((S + 1) * 8) : 0;
-    const size_t o_exit = take((size_t)n * 4), o_tent = take((size_t)w.n_tiles * 4),
-                 o_bm = take((size_t)w.n_tiles * (WIRE_TILE / 32) * 4), o_tc = take(((size_t)w.n_tiles + 1) * 4),
-                 o_tb = take(((size_t)w.n_tiles + 1) * 4), o_cons = take((size_t)S * 4), o_stop = take((size_t)S * 4),
-                 o_rsc = take(((size_t)S + 1) * 4), o_fr = take((size_t)F * 4), o_wf = take((size_t)F * sizeof(WFrame)),
-                 o_fl = take((size_t)F * 8), o_pos = take((size_t)F * 8), o_cnt = take(16),
-                 o_qf = take((size_t)F * 8), o_qc = take((size_t)F * 4), o_qfl = take(F), o_qts = take((size_t)F * 8),
-                 o_qtg = take(n), o_qb = take((size_t)n * 8), o_rs = take(F), o_rr = take((size_t)F * 4),
-                 o_nv = take((size_t)F * 4), o_qnv = take(((size_t)F + 1) * 4), o_qpo = take(((size_t)F + 1) * 4),
-                 o_rw = take((size_t)F * 4), o_resp = take((size_t)F * 16), o_sb = take(S),
-                 o_crel = take((size_t)S * 8), o_tmp = take(tmp);
-    SF_TRY(e->wire_arena.reserve(e->pool, L.size()));
-    char* A = e->wire_arena.at(0);
-    if (host_in) {
-        HIP_TRY(hipMemcpyAsync(A + o_bytes, in->bytes, n, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(A + o_soff, soff.data(), (S + 1) * 8, hipMemcpyHostToDevice, st));
-        w.bytes = (const uint8_t*)(A + o_bytes); w.soff = (const uint64_t*)(A + o_soff);
-    } else {
-        w.bytes = in->bytes; w.soff = in->stream_off;
-    }
-    w.exitv = (uint32_t*)(A + o_exit); w.tentry = (uint32_t*)(A + o_tent); w.bitmap = (uint32_t*)(A + o_bm);
-    w.tcount = (uint32_t*)(A + o_tc); w.tbase = (uint32_t*)(A + o_tb); w.consumed = (uint32_t*)(A + o_cons);
-    w.stopoff = (uint32_t*)(A + o_stop); w.resp_cnt = nullptr; w.resp_scan = (uint32_t*)(A + o_rsc);
-    w.frames = (uint32_t*)(A + o_fr); w.wf = (WFrame*)(A + o_wf); w.fl = (uint64_t*)(A + o_fl);
-    w.pos = (uint64_t*)(A + o_pos); w.counters = (uint32_t*)(A + o_cnt);
-    w.q_fid = (int64_t*)(A + o_qf); w.q_cnt = (int32_t*)(A + o_qc); w.q_flags = (uint8_t*)(A + o_qfl);
-    w.q_ts = (int64_t*)(A + o_qts); w.q_tag = (uint8_t*)(A + o_qtg); w.q_bits = (uint64_t*)(A + o_qb);
-    w.nval = (uint32_t*)(A + o_nv); w.q_nval = (uint32_t*)(A + o_qnv); w.q_poff = (uint32_t*)(A + o_qpo);
-    w.r_status = (int8_t*)(A + o_rs); w.r_rem = (int32_t*)(A + o_rr); w.r_wait = (int32_t*)(A + o_rw);
-    w.resp = (uint8_t*)(A + o_resp); w.stop = (uint8_t*)(A + o_sb); w.consumed_rel = (uint64_t*)(A + o_crel);
-    w.tmp = A + o_tmp; w.tmp_bytes = tmp;
-
-    if (e->timing) {
-        for (auto& x : e->ml_ev) if (!x) HIP_TRY(hipEventCreate(&x));
-        HIP_TRY(hipEventRecord(e->ml_ev[0], st));
-    }
-    hipError_t le = wire_frame(w, st);
-    if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("wire framing: ") + hipGetErrorString(le));
-    uint32_t nf = 0;
-    HIP_TRY(hipMemcpyAsync(&nf, w.tbase + w.n_tiles, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    uint64_t tot[2] = {0, 0};
-    if (nf) {
-        le = wire_decode(w, nf, in->now_ms, st);
-        if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("wire decode: ") + hipGetErrorString(le));
-        HIP_TRY(hipMemcpyAsync(&tot[0], w.pos + nf - 1, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&tot[1], w.fl + nf - 1, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    const uint64_t both = tot[0] + tot[1];
-    const uint32_t n_req = (uint32_t)(both >> 32), n_resp = (uint32_t)both;
-    HIP_TRY(hipMemsetAsync(e->st.err, 0, sizeof(int32_t), st));
-    if (n_req) {
-        SF_TRY(tok_work_ensure(e->tw, n_req, e->cfg.max_batch, tok_temp_query));
-        le = wire_compact(w, nf, n_req, in->now_ms, st);
-        if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("wire compact: ") + hipGetErrorString(le));
-        TokBatch b{};
-        b.n = n_req; b.flow_id = w.q_fid; b.count = w.q_cnt; b.flags = w.q_flags; b.ts = w.q_ts;
-        b.ptag = w.q_tag; b.pbits = w.q_bits; b.poff = w.q_poff;
-        TokOut o{w.r_status, w.r_rem, w.r_wait};
-        le = tok_launch(e->ts, e->tw.w, b, o, st);
-        if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("token launch: ") + hipGetErrorString(le));
-    }
-    le = wire_encode(w, nf, st);
-    if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("wire encode: ") + hipGetErrorString(le));
-    if (e->timing) HIP_TRY(hipEventRecord(e->ml_ev[1], st));
-    const bool fits = (uint64_t)n_resp * SF_WIRE_RESP_BYTES <= out->cap;
-    if (fits && n_resp) {
-        if (!out->resp) return fail(SF_ERR_INVALID, "null resp");
-        HIP_TRY(hipMemcpyAsync(out->resp, w.resp, (size_t)n_resp * SF_WIRE_RESP_BYTES, hipMemcpyDeviceToHost, st));
-    }
-    std::vector<uint32_t> roff(S + 1);
-    uint32_t handled = 0;
-    int32_t err = 0;
-    HIP_TRY(hipMemcpyAsync(roff.data(), w.resp_scan, (S + 1) * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out->consumed, w.consumed_rel, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out->stop, w.stop, S, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&handled, w.counters, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&err, e->st.err, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (e->timing) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, e->ml_ev[0], e->ml_ev[1]));
-        e->stats.wire_ms = ms;
-    }
-    for (uint32_t s = 0; s <= S; s++) out->resp_off[s] = (uint64_t)roff[s] * SF_WIRE_RESP_BYTES;
-    out->n_frames = handled; out->n_requests = n_req; out->n_responses = n_resp;
-    if (err) return fail(err, err == SF_ERR_CAPACITY ? "cluster param table capacity exceeded" : "invalid token batch");
-    if (!fits) return fail(SF_ERR_CAPACITY, "response buffer too small (n_responses * 16 bytes needed)");
-    return SF_OK;
-}
-
-int sf_cluster_sum(sf_engine* e, int64_t flow_id, int event, int64_t now_ms, int64_t* out) {
-    if (!e || !out) return fail(SF_ERR_INVALID, "null argument");
-    if (event < 0 || event >= CE_COUNT) return fail(SF_ERR_INVALID, "event");
-    std::lock_guard<std::mutex> lk(e->mu);
-    *out = 0;
-    for (size_t i = 0; i < e->host_cflow.size(); i++) {
-        if (e->host_cflow[i].flow_id != flow_id) continue;
-        HIP_TRY(tok_cluster_sum(e->ts, (uint32_t)i, event, now_ms, e->d_sum, e->stream));
-        HIP_TRY(hipMemcpyAsync(out, e->d_sum, 8, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        return SF_OK;
-    }
-    return SF_OK;
-}
-
-// ---------------------------------------------------------------- Envoy rate-limit service (sf_rls.h)
-int64_t sf_rls_flow_id(const uint8_t* key_utf8, uint32_t len) {
-    RlsKey k = rls_key_begin();
-    if (len) rls_key_feed(k, key_utf8, len);
-    return k.ok ? rls_key_id(k) : INT64_MIN;
-}
-
-int sf_rls_get_stats(sf_engine* e, sf_rls_stats* out) {
-    if (!e || !out) return fail(SF_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    *out = e->rls_stats;
-    return SF_OK;
-}
-
-int sf_request_rls(sf_engine* e, const sf_rls_batch* in, sf_rls_results* out) {
-    if (!e || !in || !out) return fail(SF_ERR_INVALID, "null argument");
-    if (e->cfg.shard_count != 1)
-        return fail(SF_ERR_UNSUPPORTED, "sf_request_rls on a sharded token server: route the descriptors by flowId");
-    const uint32_t n = in->n;
-    if (n == 0) return SF_OK;
-    if (!in->ts_ms || !in->hits_addend || !in->desc_off || !out->overall) return fail(SF_ERR_INVALID, "missing request array");
-    const bool strings = in->desc_flow_id == nullptr;
-    if (strings && (!in->domain || !in->ent_off || !in->str_off)) return fail(SF_ERR_INVALID, "missing string table");
-    const bool host_in = in->mem == SF_MEM_HOST, host_out = out->mem == SF_MEM_HOST;
-    if (n > e->cfg.max_batch) return fail(SF_ERR_CAPACITY, "more requests than max_batch");
-    std::lock_guard<std::mutex> lk(e->mu);
-    RlsBatch b{};
-    b.n = n; b.n_str = strings ? in->n_str : 0;
-    // the lengths of the tables are their last offsets: read in place, or gathered on the device for one copy
-    if (host_in) {
-        b.n_desc = in->desc_off[n];
-        if (strings && b.n_desc <= e->cfg.max_batch) { b.n_ent = in->ent_off[b.n_desc]; b.n_bytes = in->str_off[b.n_str]; }
-    } else {
-        if (!e->rls_len) SF_TRY(e->pool.alloc(&e->rls_len, 16));
-        b.desc_off = in->desc_off; b.desc_fid = in->desc_flow_id; b.ent_off = in->ent_off; b.str_off = in->str_off;
-        uint32_t len[3] = {0, 0, 0};
-        HIP_TRY(rls_lengths(b, e->rls_len, e->stream));
-        HIP_TRY(hipMemcpyAsync(len, e->rls_len, sizeof len, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        b.n_desc = len[0]; b.n_ent = len[1]; b.n_bytes = len[2];
-    }
-    if (b.n_desc > e->cfg.max_batch) return fail(SF_ERR_CAPACITY, "more descriptors than max_batch");
-    if (b.n_desc && !out->code) return fail(SF_ERR_INVALID, "null code array");
-    if (strings) {
-        if (b.n_bytes >= (1u << 31)) return fail(SF_ERR_CAPACITY, "rls strings must be < 2^31 bytes");
-        if ((b.n_ent && (!in->ent_key || !in->ent_val)) || (b.n_bytes && !in->bytes)) return fail(SF_ERR_INVALID, "missing string table");
-    }
-    const size_t nd = b.n_desc, ne = b.n_ent, ns = b.n_str;
-    SF_TRY(tok_work_ensure(e->tw, std::max(b.n_desc, 1u), e->cfg.max_batch, tok_temp_query));
-    SF_TRY(rls_work_ensure(e->rlw, std::max(n, b.n_desc), e->cfg.max_batch));
-    SF_TRY(tok_ready(e));
-    hipStream_t s = e->stream;
-    // staging: inputs (host form) then outputs (host results), 256-B aligned
-    Layout L;
-    const size_t o_ts = L.take_if(host_in, (size_t)n * 8), o_hits = L.take_if(host_in, (size_t)n * 4),
-                 o_doff = L.take_if(host_in, ((size_t)n + 1) * 4), o_fid = L.take_if(host_in && !strings, nd * 8),
-                 o_dom = L.take_if(host_in && strings, (size_t)n * 4), o_eoff = L.take_if(host_in && strings, (nd + 1) * 4),
-                 o_ek = L.take_if(host_in && strings, ne * 4), o_ev = L.take_if(host_in && strings, ne * 4),
-                 o_soff = L.take_if(host_in && strings, (ns + 1) * 4), o_bytes = L.take_if(host_in && strings, b.n_bytes);
-    const size_t r_all = L.take_if(host_out, n), r_code = L.take_if(host_out, nd), r_lim = L.take_if(host_out, nd * 4),
-                 r_rem = L.take_if(host_out, nd * 4), r_fid = L.take_if(host_out, nd * 8);
-    SF_TRY(e->rls_stage.reserve(e->pool, std::max<size_t>(L.size(), 16)));
-    char* base = e->rls_stage.at(0);
-    if (host_in) {
-        auto up = [&](size_t off, const void* src, size_t bytes) -> int {
-            if (bytes) HIP_TRY(hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, s));
-            return SF_OK;
-        };
-        SF_TRY(up(o_ts, in->ts_ms, (size_t)n * 8)); SF_TRY(up(o_hits, in->hits_addend, (size_t)n * 4));
-        SF_TRY(up(o_doff, in->desc_off, ((size_t)n + 1) * 4));
-        b.ts = (const int64_t*)(base + o_ts); b.hits = (const int32_t*)(base + o_hits);
-        b.desc_off = (const uint32_t*)(base + o_doff);
-        if (!strings) {
-            SF_TRY(up(o_fid, in->desc_flow_id, nd * 8));
-            b.desc_fid = (const int64_t*)(base + o_fid);
-        } else {
-            SF_TRY(up(o_dom, in->domain, (size_t)n * 4)); SF_TRY(up(o_eoff, in->ent_off, (nd + 1) * 4));
-            SF_TRY(up(o_ek, in->ent_key, ne * 4)); SF_TRY(up(o_ev, in->ent_val, ne * 4));
-            SF_TRY(up(o_soff, in->str_off, (ns + 1) * 4)); SF_TRY(up(o_bytes, in->bytes, b.n_bytes));
-            b.domain = (const uint32_t*)(base + o_dom); b.ent_off = (const uint32_t*)(base + o_eoff);
-            b.ent_key = (const uint32_t*)(base + o_ek); b.ent_val = (const uint32_t*)(base + o_ev);
-            b.str_off = (const uint32_t*)(base + o_soff); b.bytes = (const uint8_t*)(base + o_bytes);
-        }
-    } else {
-        b.ts = in->ts_ms; b.hits = in->hits_addend; b.desc_off = in->desc_off; b.desc_fid = in->desc_flow_id;
-        b.domain = in->domain; b.ent_off = in->ent_off; b.ent_key = in->ent_key; b.ent_val = in->ent_val;
-        b.str_off = in->str_off; b.bytes = in->bytes;
-    }
-    RlsOut o{};
-    if (host_out) {
-        o.overall = (uint8_t*)(base + r_all); o.code = (uint8_t*)(base + r_code); o.limit = (int32_t*)(base + r_lim);
-        o.remaining = (int32_t*)(base + r_rem); o.flow_id = (int64_t*)(base + r_fid);
-    } else {
-        o.overall = out->overall; o.code = out->code; o.limit = out->limit; o.remaining = out->remaining; o.flow_id = out->flow_id;
-    }
-    HIP_TRY(hipMemsetAsync(e->st.err, 0, sizeof(int32_t), s));
-    hipError_t le = rls_launch(e->ts, e->tw.w, e->rlw.w, b, o, e->rls_wave_min, s);
-    if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("rls launch: ") + hipGetErrorString(le));
-    int32_t err = 0;
-    RlsCounters c{};
-    HIP_TRY(hipMemcpyAsync(&err, e->st.err, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&c, e->rlw.w.ctr, sizeof c, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (err) return fail(err, "malformed rls batch (offsets must not decrease, string indices must be < n_str, ts_ms must be >= 0)");
-    if (host_out) {
-        HIP_TRY(hipMemcpyAsync(out->overall, o.overall, n, hipMemcpyDeviceToHost, s));
-        if (nd) {
-            HIP_TRY(hipMemcpyAsync(out->code, o.code, nd, hipMemcpyDeviceToHost, s));
-            if (out->limit) HIP_TRY(hipMemcpyAsync(out->limit, o.limit, nd * 4, hipMemcpyDeviceToHost, s));
-            if (out->remaining) HIP_TRY(hipMemcpyAsync(out->remaining, o.remaining, nd * 4, hipMemcpyDeviceToHost, s));
-            if (out->flow_id) HIP_TRY(hipMemcpyAsync(out->flow_id, o.flow_id, nd * 8, hipMemcpyDeviceToHost, s));
-        }
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    sf_rls_stats& st = e->rls_stats;
-    st.requests += n; st.descriptors += nd; st.error_requests += c.error_requests; st.no_rule += c.no_rule;
-    st.segs_lane += c.segs_lane; st.segs_wave += c.segs_wave; st.chunks += c.chunks;
-    st.chunks_serial += c.chunks_serial; st.rounds += c.rounds;
-    return SF_OK;
-}
-
-// ---------------------------------------------------------------- cluster concurrency tokens
-// state of the concurrency tokens present; caller holds e->mu
-static int cc_ready(sf_engine* e) {
-    SF_TRY(tok_ready(e));
-    if (!e->cc.cs.now || !e->cc.cs.cfg || !e->cc.cs.ctr) return cc_tables(e, nullptr);
-    return SF_OK;
-}
-
-static int cc_read_counters(sf_engine* e) {
-    HIP_TRY(hipMemcpyAsync(&e->cc.ctr, e->cc.cs.ctr, sizeof(CcCounters), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return SF_OK;
-}
-
-// The pool holds at least `min_cap` slots and at least `need_free` free ones:
-// a larger array with the old one copied and the new slots pushed, so slot
-// numbers and live ids stay valid.  SF_ERR_CAPACITY past 2^28 slots, nothing changed.
-static int cc_pool_ensure(sf_engine* e, uint64_t need_free, uint64_t min_cap) {
-    CcHost& c = e->cc;
-    CcState& cs = c.cs;
-    const uint64_t cap = cs.cap, free_now = c.ctr.top;
-    if (free_now >= need_free && cap >= min_cap && cap) return SF_OK;
-    uint64_t ncap = std::max<uint64_t>(min_cap, cap);
-    if (free_now < need_free) ncap = std::max<uint64_t>({ncap, cap + (need_free - free_now), 2 * cap});
-    if (!cap && !min_cap) ncap = std::max<uint64_t>(ncap, 1024);
-    ncap = std::max<uint64_t>(ncap, 1);
-    if (ncap > CC_MAX_SLOTS) ncap = CC_MAX_SLOTS;
-    if (ncap < min_cap || ncap - cap + free_now < need_free)
-        return fail(SF_ERR_CAPACITY, "concurrency token pool: more than 2^28 slots needed");
-    if (ncap == cap) return SF_OK;
-    hipStream_t s = e->stream;
-    CcSlot* slots = nullptr; uint32_t* stack = nullptr; uint32_t* claim = nullptr;
-    DevPool fresh{HIP_MEM};                    // (the new arrays; an early return frees them and the old pool stays)
-    SF_TRY(fresh.alloc(&slots, ncap * sizeof(CcSlot)));
-    SF_TRY(fresh.alloc(&stack, ncap * 4));
-    SF_TRY(fresh.alloc(&claim, ncap * 4));
-    HIP_TRY(hipMemsetAsync(slots, 0, ncap * sizeof(CcSlot), s));
-    if (cap) {
-        HIP_TRY(hipMemcpyAsync(slots, cs.slots, cap * sizeof(CcSlot), hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(stack, cs.stack, cap * 4, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(claim, cs.claim, cap * 4, hipMemcpyDeviceToDevice, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    e->pool.release_all(cs.slots, cs.stack, cs.claim);
-    e->pool.adopt(fresh);
-    cs.slots = slots; cs.stack = stack; cs.claim = claim; cs.cap = (uint32_t)ncap;
-    HIP_TRY(cc_push_range(cs, (uint32_t)cap, (uint32_t)ncap, s));
-    if (cap) c.grows++;
-    return cc_read_counters(e);
-}
-
-int sf_load_concurrent_config(sf_engine* e, const sf_concurrent_config* cfg, uint32_t n) {
-    if (!e || (n && !cfg)) return fail(SF_ERR_INVALID, "null argument");
-    for (uint32_t i = 0; i < n; i++)
-        if (cfg[i].resource_timeout_ms <= 0 || cfg[i].client_offline_time_ms <= 0)      // FlowRuleUtil.java:195
-            return fail(SF_ERR_INVALID, "concurrent config: time-outs must be > 0");
-    std::lock_guard<std::mutex> lk(e->mu);
-    e->cc.cfg.assign(cfg, cfg + n);
-    return e->cc.cs.cfg ? cc_tables(e, nullptr) : SF_OK;
-}
-
-int sf_concurrent_reserve(sf_engine* e, uint64_t tokens) {
-    if (!e) return fail(SF_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    SF_TRY(cc_ready(e));
-    return cc_pool_ensure(e, 0, std::max<uint64_t>(tokens, 1));
-}
-
-int sf_request_concurrent(sf_engine* e, const sf_concurrent_batch* in, sf_concurrent_results* out) {
-    if (!e || !in || !out || !out->status || !out->token_id) return fail(SF_ERR_INVALID, "null argument");
-    if (in->n == 0) return SF_OK;
-    if (!in->op || !in->id || !in->count || !in->client || !in->ts_ms) return fail(SF_ERR_INVALID, "missing request array");
-    if (e->cfg.shard_count > 255) return fail(SF_ERR_UNSUPPORTED, "concurrency tokens: at most 255 shards (token id layout)");
-    std::lock_guard<std::mutex> lk(e->mu);
-    const uint32_t n = in->n;
-    SF_TRY(cc_ready(e));
-    SF_TRY(cc_work_ensure(e->cc.ws, n, (uint32_t)e->host_cflow.size(), cc_temp_query));
-    SF_TRY(cc_pool_ensure(e, n, 0));     // a slot for every request, before any state changes
-    CcHost& c = e->cc;
-    hipStream_t s = e->stream;
-    Layout L;
-    const size_t off_op = L.take(n), off_id = L.take((size_t)n * 8), off_cnt = L.take((size_t)n * 4);
-    const size_t off_cl = L.take((size_t)n * 4), off_ts = L.take((size_t)n * 8), off_st = L.take(n), off_tid = L.take((size_t)n * 8);
-    SF_TRY(c.stage.reserve(e->pool, L.size()));
-    char* base = c.stage.at(0);
-    CcBatch b{};
-    b.n = n;
-    if (in->mem == SF_MEM_HOST) {
-        HIP_TRY(hipMemcpyAsync(base + off_op, in->op, n, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(base + off_id, in->id, (size_t)n * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(base + off_cnt, in->count, (size_t)n * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(base + off_cl, in->client, (size_t)n * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(base + off_ts, in->ts_ms, (size_t)n * 8, hipMemcpyHostToDevice, s));
-        b.op = (const uint8_t*)(base + off_op); b.id = (const int64_t*)(base + off_id);
-        b.count = (const int32_t*)(base + off_cnt); b.client = (const uint32_t*)(base + off_cl);
-        b.ts = (const int64_t*)(base + off_ts);
-    } else {
-        b.op = in->op; b.id = in->id; b.count = in->count; b.client = in->client; b.ts = in->ts_ms;
-    }
-    const bool host_out = out->mem == SF_MEM_HOST;
-    CcOut o{host_out ? (int8_t*)(base + off_st) : out->status, host_out ? (int64_t*)(base + off_tid) : out->token_id};
-    HIP_TRY(hipMemsetAsync(e->st.err, 0, sizeof(int32_t), s));
-    hipError_t le = cc_launch(e->ts, c.cs, c.ws.w, b, o, s);
-    if (le != hipSuccess) return fail(SF_ERR_DEVICE, std::string("concurrent launch: ") + hipGetErrorString(le));
-    if (host_out) {
-        HIP_TRY(hipMemcpyAsync(out->status, o.status, n, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out->token_id, o.token_id, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-    }
-    int32_t err = 0;
-    HIP_TRY(hipMemcpyAsync(&err, e->st.err, 4, hipMemcpyDeviceToHost, s));
-    SF_TRY(cc_read_counters(e));
-    if (err) return fail(err, err == SF_ERR_CAPACITY ? "concurrency token pool exhausted"
-                                                     : "invalid concurrent batch (a request owned by another shard?)");
-    return SF_OK;
-}
-
-int sf_concurrent_expire(sf_engine* e, int64_t now_ms, const uint8_t* client_online, uint32_t n_clients,
-                         uint32_t* n_expired) {
-    if (!e || (n_clients && !client_online)) return fail(SF_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    SF_TRY(cc_ready(e));
-    CcHost& c = e->cc;
-    SF_TRY(c.online.reserve(e->pool, n_clients));
-    uint8_t* online = (uint8_t*)c.online.p;
-    if (n_clients) HIP_TRY(hipMemcpyAsync(online, client_online, n_clients, hipMemcpyHostToDevice, e->stream));
-    const uint64_t before = c.ctr.expired;
-    HIP_TRY(cc_expire(e->ts, c.cs, now_ms, online, n_clients, e->stream));
-    SF_TRY(cc_read_counters(e));
-    if (n_expired) *n_expired = (uint32_t)(c.ctr.expired - before);
-    return SF_OK;
-}
-
-int sf_concurrent_now(sf_engine* e, int64_t flow_id, int64_t* now_calls) {
-    if (!e || !now_calls) return fail(SF_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (flow_id > 0)
-        for (size_t i = 0; i < e->host_cflow.size(); i++) {
-            if (e->host_cflow[i].flow_id != flow_id) continue;
-            SF_TRY(cc_ready(e));
-            int32_t v = 0;
-            HIP_TRY(hipStreamSynchronize(e->stream));
-            HIP_TRY(hipMemcpy(&v, e->cc.cs.now + i, 4, hipMemcpyDeviceToHost));
-            *now_calls = v;
-            return SF_OK;
-        }
-    return fail(SF_ERR_INVALID, "sf_concurrent_now: flowId not loaded");
-}
-
-int sf_read_token(sf_engine* e, int64_t token_id, sf_token_node* out) {
-    if (!e || !out) return fail(SF_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    const uint64_t tid = (uint64_t)token_id;
-    const uint32_t slot = (uint32_t)tid & CC_SLOT_MASK, gen = (uint32_t)(tid >> CC_SLOT_BITS) & CC_SLOT_MASK;
-    if ((tid >> 56) != (uint64_t)e->cfg.shard_index + 1 || slot >= e->cc.cs.cap)
-        return fail(SF_ERR_INVALID, "sf_read_token: not a live token");
-    CcSlot sl;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(&sl, e->cc.cs.slots + slot, sizeof sl, hipMemcpyDeviceToHost));
-    if (!sl.live || sl.gen != gen) return fail(SF_ERR_INVALID, "sf_read_token: not a live token");
-    out->flow_id = sl.flow_id; out->client_deadline_ms = sl.client_deadline; out->resource_deadline_ms = sl.resource_deadline;
-    out->count = sl.count; out->client = sl.client;
-    return SF_OK;
-}
-
-int sf_concurrent_get_stats(sf_engine* e, sf_concurrent_stats* out) {
-    if (!e || !out) return fail(SF_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    const CcHost& c = e->cc;
-    out->live_tokens = (uint64_t)c.cs.cap - c.ctr.top; out->pool_capacity = c.cs.cap; out->pool_grows = c.grows;
-    out->chunks = c.ctr.chunks; out->chunks_all_pass = c.ctr.chunks_all_pass; out->rounds = c.ctr.rounds;
-    out->expired = c.ctr.expired;
-    return SF_OK;
-}
 
 // ---------------------------------------------------------------- node-wide aggregate (RCCL)
 int sf_comm_unique_id(uint8_t* out, size_t len) {
@@ -3138,7 +1979,7 @@ int sf_comm_init(sf_engine* e, int nranks, int rank, const uint8_t* id, size_t l
     std::memcpy(uid.internal, id, NCCL_UNIQUE_ID_BYTES);
     ncclResult_t r = ncclCommInitRank(&e->comm, nranks, uid, rank);
     if (r != ncclSuccess) { e->comm = nullptr; return fail(SF_ERR_DEVICE, std::string("ncclCommInitRank: ") + ncclGetErrorString(r)); }
-    if (!e->agg) SF_TRY(e->pool.alloc(&e->agg, 4096 * sizeof(int64_t)));
+    if (!e->sx.agg) SF_TRY(e->pool.alloc(&e->sx.agg, 4096 * sizeof(int64_t)));
     return SF_OK;
 }
 
@@ -3146,15 +1987,15 @@ int sf_set_report_entry_node(sf_engine* e, const sf_node_state* node) {
     if (!e) return fail(SF_ERR_INVALID, "null engine");
     std::lock_guard<std::mutex> lk(e->mu);
     SF_TRY(en_fence(e));
-    if (!node) { e->report_set = false; return SF_OK; }
-    EntryNode& r = e->report;
+    if (!node) { e->rep.report_set = false; return SF_OK; }
+    EntryNode& r = e->rep.report;
     r = EntryNode{};
     const int64_t mrt = e->cfg.statistic_max_rt;
     for (int i = 0; i < SF_MAX_SAMPLE_COUNT; i++)
         r.second[i] = i < e->cfg.sample_count ? from_abi_bucket(node->second[i], mrt) : Bucket{WS_NONE, 0, 0, 0, 0, 0, 0, mrt};
     for (int i = 0; i < MINUTE; i++) r.minute[i] = from_abi_bucket(node->minute[i], mrt);
     r.threads = node->cur_thread_num;
-    e->report_set = true;
+    e->rep.report_set = true;
     return SF_OK;
 }
 
@@ -3165,7 +2006,7 @@ int sf_entry_node_allreduce(sf_engine* e, sf_node_state* out) {
     if (!e->comm) return fail(SF_ERR_INVALID, "sf_comm_init first");
     const int S = e->cfg.sample_count, nb = S + MINUTE;
     hipStream_t s = e->stream;
-    int64_t *ws = e->agg, *gws = ws + nb, *vals = gws + nb, *minrt = vals + nb * 6 + 1;
+    int64_t *ws = e->sx.agg, *gws = ws + nb, *vals = gws + nb, *minrt = vals + nb * 6 + 1;
     HIP_TRY(launch_en_pack_ws(e->en, S, ws, s));
     auto nc = [&](ncclResult_t r, const char* what) -> int {
         return r == ncclSuccess ? SF_OK : fail(SF_ERR_DEVICE, std::string(what) + ": " + ncclGetErrorString(r));
@@ -3336,200 +2177,5 @@ int sf_heavy_profile_read(sf_engine* e, sf_heavy_profile* out, uint32_t cap, uin
 }
 
 
-// ---------------------------------------------------------------- DegradeSlot circuit breakers
-// DegradeRule.equals (DegradeRule.java:153-164, AbstractRule.equals :76-93):
-// resource, limitApp (always "default" here) and the six fields, doubles by
-// Double.compare (bit pattern; every NaN equal).
-static bool dg_same_double(double a, double b) {
-    if (a != a && b != b) return true;
-    int64_t x, y;
-    std::memcpy(&x, &a, 8); std::memcpy(&y, &b, 8);
-    return x == y;
-}
-static bool dg_rule_equal(const sf_degrade_rule& a, const sf_degrade_rule& b) {
-    return a.resource == b.resource && a.grade == b.grade && dg_same_double(a.count, b.count) &&
-           a.time_window_s == b.time_window_s && a.min_request_amount == b.min_request_amount &&
-           dg_same_double(a.slow_ratio_threshold, b.slow_ratio_threshold) && a.stat_interval_ms == b.stat_interval_ms;
-}
-
-int sf_load_degrade_rules(sf_engine* e, const sf_degrade_rule* rules, uint32_t n, uint32_t* n_loaded) {
-    if (!e || (n && !rules)) return fail(SF_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    SF_TRY(drain(e));
-    // buildCircuitBreakers (DegradeRuleManager.java:236-265): valid rules, list order per resource.
-    // Everything is built in locals first; the engine's tables are swapped only
-    // after every check and allocation succeeded (a failed load keeps the old rules).
-    std::vector<uint32_t> loc, valid;
-    for (uint32_t i = 0; i < n; i++) {
-        if (!dg_valid(rules[i])) continue;
-        uint32_t l;
-        if (!local_of(e, rules[i].resource, &l)) return fail(SF_ERR_INVALID, "degrade rule resource outside this shard");
-        valid.push_back(i);
-        loc.push_back(l);
-    }
-    const uint32_t nv = (uint32_t)valid.size();
-    std::vector<uint32_t> order(nv);
-    for (uint32_t i = 0; i < nv; i++) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return loc[a] < loc[b]; });
-    std::vector<uint32_t> rr_of(e->R, 0), off;
-    std::vector<DevBreakerRule> dr(nv);
-    std::vector<sf_breaker_state> st(nv);
-    std::vector<uint32_t> pos(nv, 0);
-    uint32_t n_rres = 0;
-    for (uint32_t p = 0; p < nv; p++) {
-        const uint32_t v = order[p];
-        if (p == 0 || loc[order[p - 1]] != loc[v]) {
-            off.push_back(p);
-            n_rres++;
-        }
-        if (p - off.back() >= SF_MAX_BREAKERS_PER_RESOURCE)
-            return fail(SF_ERR_UNSUPPORTED, "more than SF_MAX_BREAKERS_PER_RESOURCE degrade rules on one resource");
-        const sf_degrade_rule& r = rules[valid[v]];
-        dr[p] = make_dev_breaker_rule(r);
-        st[p] = sf_breaker_state{SF_CB_CLOSED, 0, 0, DG_WS_NONE, 0, 0};
-        pos[v] = p;
-    }
-    off.push_back(nv);
-    for (auto& x : rr_of) x = n_rres;
-    for (uint32_t k = 0; k < n_rres; k++) rr_of[loc[order[off[k]]]] = k;
-    // getExistingSameCbOrNew (DegradeRuleManager.java:151-163): a rule equal to
-    // one of the resource's current breakers keeps that breaker and its state.
-    // The reference hands the SAME breaker object to two equal new rules of one
-    // resource; that aliasing is refused rather than approximated.
-    if (nv && !e->dg_rules.empty()) {
-        std::vector<sf_breaker_state> old(e->dg_rules.size());
-        for (size_t k = 0; k < old.size(); k++)
-            HIP_TRY(hipMemcpy(&old[k], e->dg.state + e->dg_pos[k], sizeof(sf_breaker_state), hipMemcpyDeviceToHost));
-        std::vector<uint8_t> taken(old.size(), 0);
-        for (uint32_t v = 0; v < nv; v++) {
-            const sf_degrade_rule& r = rules[valid[v]];
-            for (size_t k = 0; k < old.size(); k++) {
-                if (!dg_rule_equal(r, e->dg_rules[k])) continue;
-                if (taken[k])
-                    return fail(SF_ERR_UNSUPPORTED, "two equal degrade rules would share one existing breaker");
-                taken[k] = 1;
-                st[pos[v]] = old[k];
-                break;
-            }
-        }
-    }
-    uint32_t *d_rr = nullptr, *d_off = nullptr;
-    DevBreakerRule* d_rules = nullptr;
-    sf_breaker_state* d_st = nullptr;
-    DevPool fresh{HIP_MEM};                    // (the new tables, freed by an early return)
-    SF_TRY(fresh.alloc(&d_rr, nz((size_t)e->R * 4)));
-    SF_TRY(fresh.alloc(&d_off, nz(off.size() * 4)));
-    SF_TRY(fresh.alloc(&d_rules, nz((size_t)nv * sizeof(DevBreakerRule))));
-    SF_TRY(fresh.alloc(&d_st, nz((size_t)nv * sizeof(sf_breaker_state))));
-    HIP_TRY(hipMemcpy(d_rr, rr_of.data(), (size_t)e->R * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-    if (nv) HIP_TRY(hipMemcpy(d_rules, dr.data(), (size_t)nv * sizeof(DevBreakerRule), hipMemcpyHostToDevice));
-    if (nv) HIP_TRY(hipMemcpy(d_st, st.data(), (size_t)nv * sizeof(sf_breaker_state), hipMemcpyHostToDevice));
-    e->pool.release_all(e->dg.rr_of, e->dg.off, e->dg.rules, e->dg.state);
-    e->pool.adopt(fresh);
-    e->dg = DegradeDev{};
-    e->dg.rr_of = d_rr; e->dg.off = d_off; e->dg.rules = d_rules; e->dg.state = d_st;
-    e->dg.n_rres = n_rres;
-    // DegradeSlot inside sf_submit's chain (sf_decide.h decide_segment)
-    e->st.dg_rr_of = n_rres ? d_rr : nullptr;
-    e->st.dg_off = d_off; e->st.dg_rules = d_rules; e->st.dg_state = d_st; e->st.dg_n = n_rres;
-    e->dg_pos = pos;
-    e->dg_rules.clear();
-    for (uint32_t v = 0; v < nv; v++) e->dg_rules.push_back(rules[valid[v]]);
-    uint32_t kb = 1;
-    while ((1ull << kb) <= n_rres) kb++;                        // keys 0..n_rres (n_rres = no breaker)
-    e->dg.key_bits = kb;
-    dg_drop_sort_tmp(e->dgw);                                   // re-sized for the new key width
-    {   // the routing summary reads dg_rr_of
-        hipError_t re = launch_rdesc(e->st, e->stream);
-        if (re == hipSuccess) re = hipStreamSynchronize(e->stream);
-        if (re != hipSuccess) return fail(SF_ERR_DEVICE, std::string("rdesc: ") + hipGetErrorString(re));
-    }
-    if (n_loaded) *n_loaded = nv;
-    return SF_OK;
-}
-
-int sf_degrade_submit(sf_engine* e, const sf_event_batch* in, sf_verdicts* out) {
-    if (!e || !in || !out || !out->status) return fail(SF_ERR_INVALID, "null argument");
-    if (in->n == 0) return SF_OK;
-    if (!in->res_id || !in->ts_ms || !in->flags) return fail(SF_ERR_INVALID, "missing event array");
-    if (in->n > e->cfg.max_batch) return fail(SF_ERR_CAPACITY, "batch larger than max_batch");
-    std::lock_guard<std::mutex> lk(e->mu);
-    SF_TRY(drain(e));
-    const uint32_t n = in->n;
-    SF_TRY(dg_work_ensure(e->dgw, n, e->dg.n_rres, e->dg.key_bits, dg_temp_query));
-    hipStream_t s = e->stream;
-    DegradeBatch b{};
-    b.n = n; b.shard_count = e->cfg.shard_count; b.shard_index = e->cfg.shard_index; b.R = e->R;
-    b.last_ts = e->st.last_ts;
-    uint8_t* status = out->status;
-    uint16_t* rule = out->rule_idx;
-    int32_t* wait = out->wait_ms;
-    const bool host_in = in->mem == SF_MEM_HOST, host_out = out->mem == SF_MEM_HOST;
-    // AuthoritySlot precedes DegradeSlot: entries the loaded rules block are marked first
-    const bool auth = e->auth.of && in->origin;
-    const uint32_t* origin = in->origin;
-    if (host_in || host_out) {
-        Layout L;
-        const size_t o_res = L.take_if(host_in, (size_t)n * 4), o_ts = L.take_if(host_in, (size_t)n * 8);
-        const size_t o_fl = L.take_if(host_in, n), o_er = L.take_if(host_in && in->entry_ref, (size_t)n * 8);
-        const size_t o_ct = L.take_if(host_in && in->create_ts, (size_t)n * 8), o_st = L.take_if(host_out, n);
-        const size_t o_ru = L.take_if(host_out && rule, (size_t)n * 2), o_wa = L.take_if(host_out && wait, (size_t)n * 4);
-        const size_t o_og = L.take_if(host_in && auth, (size_t)n * 4);
-        SF_TRY(e->dg_stage.reserve(e->pool, L.size()));
-        char* base = e->dg_stage.at(0);
-        auto up = [&](size_t off, const void* src, size_t bytes) -> const void* {
-            if (!src) return nullptr;
-            hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, s);
-            return base + off;
-        };
-        if (host_in) {
-            b.res = (const uint32_t*)up(o_res, in->res_id, (size_t)n * 4);
-            b.ts = (const int64_t*)up(o_ts, in->ts_ms, (size_t)n * 8);
-            b.flags = (const uint8_t*)up(o_fl, in->flags, n);
-            b.eref = (const int64_t*)up(o_er, in->entry_ref, (size_t)n * 8);
-            b.cts = (const int64_t*)up(o_ct, in->create_ts, (size_t)n * 8);
-            if (auth) origin = (const uint32_t*)up(o_og, in->origin, (size_t)n * 4);
-        }
-        if (host_out) {
-            status = (uint8_t*)(base + o_st);
-            rule = rule ? (uint16_t*)(base + o_ru) : nullptr;
-            wait = wait ? (int32_t*)(base + o_wa) : nullptr;
-        }
-    }
-    if (!host_in) {
-        b.res = in->res_id; b.ts = in->ts_ms; b.flags = in->flags; b.eref = in->entry_ref; b.cts = in->create_ts;
-    }
-    if (auth) {                                  // (drained: the slot's array is free)
-        Slot& sl = e->slot[e->cur];
-        SF_TRY(slot_aflags(e, sl));
-        HIP_TRY(launch_auth_mark(e->auth, b.res, origin, b.flags, n, (uint8_t)(SF_EV_BLOCKED | EVF_AUTH), sl.aflags, s));
-        b.flags = sl.aflags;
-        b.marked = 1;
-    }
-    HIP_TRY(hipMemsetAsync(e->dgw.w.err, 0, 4, s));
-    HIP_TRY(dg_launch(e->dg, e->dgw.w, b, status, rule, wait, s));
-    int err = 0;
-    HIP_TRY(hipMemcpyAsync(&err, e->dgw.w.err, 4, hipMemcpyDeviceToHost, s));
-    if (host_out) {
-        HIP_TRY(hipMemcpyAsync(out->status, status, n, hipMemcpyDeviceToHost, s));
-        if (rule) HIP_TRY(hipMemcpyAsync(out->rule_idx, rule, (size_t)n * 2, hipMemcpyDeviceToHost, s));
-        if (wait) HIP_TRY(hipMemcpyAsync(out->wait_ms, wait, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    if (err & 1) return fail(SF_ERR_INVALID, "event resource outside this shard");
-    if (err & 2) return fail(SF_ERR_INVALID, "EXIT without a valid entry_ref or create_ts");
-    if (err & 4) return fail(SF_ERR_INVALID, "event times must be non-decreasing (within and across batches)");
-    return SF_OK;
-}
-
-int sf_read_breaker(sf_engine* e, uint32_t k, sf_breaker_state* out) {
-    if (!e || !out) return fail(SF_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (k >= e->dg_pos.size()) return fail(SF_ERR_INVALID, "breaker index");
-    HIP_TRY(hipMemcpy(out, e->dg.state + e->dg_pos[k], sizeof *out, hipMemcpyDeviceToHost));
-    if (out->window_start == DG_WS_NONE) out->window_start = SF_WS_ABSENT;
-    return SF_OK;
-}
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // sf_mem.h — who owns device and pinned host memory (host code only; no HIP
 // header, so tests/mem_check.cpp runs it on malloc under the sanitizers).
 //
-//   MemOps   the seam to the backend: sf_engine.cpp plugs in hipMalloc /
+//   MemOps   the seam to the backend: sf_host.h plugs in hipMalloc /
 //            hipFree / hipHostMalloc / hipHostFree, the host test malloc / free
 //            with a counter that fails the k-th allocation.  Nothing else.
 //   DevPool  owns every pointer it handed out; what is left is freed by clear()
@@ -10,6 +10,9 @@
 //   GrowBuf  a grow-only buffer: after a failed reserve it is empty, so the next
 //            call allocates again.
 //   Layout   offsets of the pieces of one staging buffer, 256-byte aligned.
+//   StagePlan  one batch's arrays, each declared once: its room in the staging
+//            buffer, its copy and the device pointer the kernels get (host
+//            form), or the caller's pointer in place (device form).
 //
 // The rule for a set of buffers that grow together (a Work set, the token /
 // concurrency / degrade work sets, ...): the set's capacity or first-use flag
@@ -17,6 +20,7 @@
 // failure the set's pool is cleared and its struct reset, so capacity reads 0
 // and the next call builds the set again.
 #pragma once
+#include <assert.h>
 #include <stddef.h>
 
 #include <vector>
@@ -114,6 +118,75 @@ struct Layout {
     size_t size() const { return off_; }
 private:
     size_t off_ = 0;
+};
+
+// The staging of one batch: every array is declared once, with the address of
+// the pointer the kernels read.  A host-form array gets room in the staging
+// buffer (Layout's offsets, in declaration order) and a copy; a device-form
+// array is read or written in place: its pointer is the caller's, it takes no
+// room and no copy.  The input and the result form are independent.  `on`
+// false: the pointer is null, no room, no copy, in either form.
+//   size()   the room to reserve (the site decides when its buffer may move)
+//   bind()   every staged pointer = base + its offset
+//   upload() / download()   the copies in declaration order through
+//            copy(dst, src, bytes) -> int; pieces of 0 bytes are skipped, the
+//            first error is returned
+// The pieces sit in an inline array: a plan never allocates.
+class StagePlan {
+public:
+    static constexpr int CAP = 48;
+    StagePlan(bool host_in, bool host_out) : host_in_(host_in), host_out_(host_out) {}
+    StagePlan(const StagePlan&) = delete;
+    StagePlan& operator=(const StagePlan&) = delete;
+
+    // an input array of `bytes` at src; room: what the kernels may read past it
+    template <class T> void in(bool on, const T** dev, const void* src, size_t bytes, size_t room = 0) {
+        if (!on) *dev = nullptr;
+        else if (!host_in_) *dev = (const T*)src;
+        else add(dev, set<const T>, room ? room : bytes, (void*)src, bytes, UP);
+    }
+    // a result array of `bytes`, copied back to dst when asked
+    template <class T> void out(bool on, T** dev, void* dst, size_t bytes, bool copy_back = true) {
+        if (!on) *dev = nullptr;
+        else if (!host_out_) *dev = (T*)dst;
+        else add(dev, set<T>, bytes, dst, bytes, copy_back ? DOWN : NONE);
+    }
+    // device-only room, in either form
+    template <class T> void scratch(bool on, T** dev, size_t bytes) {
+        if (!on) *dev = nullptr;
+        else add(dev, set<T>, bytes, nullptr, 0, NONE);
+    }
+    template <class T> void scratch(T** dev, size_t bytes) { scratch(true, dev, bytes); }
+
+    size_t size() const { return lay_.size(); }
+    void bind(void* base) {
+        base_ = (char*)base;
+        for (int i = 0; i < n_; i++) e_[i].set(e_[i].slot, base_ + e_[i].off);
+    }
+    template <class F> int upload(F&& copy) const {
+        for (int i = 0; i < n_; i++)
+            if (e_[i].dir == UP && e_[i].bytes) SF_TRY(copy((void*)(base_ + e_[i].off), (const void*)e_[i].host, e_[i].bytes));
+        return 0;
+    }
+    template <class F> int download(F&& copy) const {
+        for (int i = 0; i < n_; i++)
+            if (e_[i].dir == DOWN && e_[i].bytes) SF_TRY(copy(e_[i].host, (const void*)(base_ + e_[i].off), e_[i].bytes));
+        return 0;
+    }
+
+private:
+    enum Dir : unsigned char { NONE, UP, DOWN };
+    struct Piece { void* slot; void (*set)(void*, char*); size_t off; void* host; size_t bytes; Dir dir; };
+    template <class T> static void set(void* slot, char* p) { *(T**)slot = (T*)p; }
+    void add(void* slot, void (*st)(void*, char*), size_t room, void* host, size_t bytes, Dir dir) {
+        assert(n_ < CAP);
+        e_[n_++] = Piece{slot, st, lay_.take(room), host, bytes, dir};
+    }
+    bool host_in_, host_out_;
+    Layout lay_;
+    char* base_ = nullptr;
+    int n_ = 0;
+    Piece e_[CAP];
 };
 
 }  // namespace sf

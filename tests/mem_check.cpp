@@ -7,14 +7,21 @@
 //   - the work sets (TokWork, CcWork, DegradeWork): with any one allocation of
 //     a growth step failing, the set reads capacity 0, every pointer null and
 //     nothing leaked, and the retry builds the whole set;
-//   - Layout: the offsets of the token request staging and of the host batch
-//     staging equal the align_up chains the engine computed by hand before.
+//   - Layout: its own offsets;
+//   - StagePlan: the rooms of the token request staging and of the host batch
+//     staging lie where the align_up chains the engine computed by hand put
+//     them, inside size(), apart, aligned and in declaration order; upload and
+//     download copy exactly the declared bytes of the pieces that asked, in
+//     order, and stop at a failing copy; device-form pieces are the caller's
+//     pointers with no room and no copy; a piece that is off is null.
 // Built with the address and undefined-behaviour sanitizers: a double free, a
 // leak at exit or an access outside a block ends the run.  Exit status 0 and
 // " 0 failures": every case as expected.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <set>
+#include <vector>
 
 #include "../sentinel_amd/csrc/sf_worksets.h"
 
@@ -197,26 +204,131 @@ static void dg_cases() {
 // ---------------------------------------------------------------- Layout
 static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// sf_request_tokens' staging as it was written before Layout
-static void token_chain(uint32_t n, uint32_t n_vals, bool has_param, bool param_off) {
+// ---------------------------------------------------------------- StagePlan
+// One declared piece and what the checks know about it.
+struct Decl { int kind; bool on; size_t bytes, room; bool copy_back; };   // kind: 0 in, 1 out, 2 scratch
+static Decl d_in(bool on, size_t bytes, size_t room = 0) { return Decl{0, on, bytes, room ? room : bytes, false}; }
+static Decl d_out(bool on, size_t bytes, bool copy_back = true) { return Decl{1, on, bytes, bytes, copy_back}; }
+static Decl d_scratch(bool on, size_t bytes) { return Decl{2, on, bytes, bytes, false}; }
+
+static const int COPY_ERR = -7;
+struct CopyLog {
+    struct Rec { void* dst; const void* src; size_t bytes; };
+    std::vector<Rec> recs;
+    long fail_at = 0;                                  // k: the k-th call fails (after k - 1 copies)
+    int operator()(void* dst, const void* src, size_t bytes) {
+        if (fail_at && (long)recs.size() + 1 == fail_at) { recs.push_back(Rec{nullptr, nullptr, 0}); return COPY_ERR; }
+        std::memcpy(dst, src, bytes);
+        recs.push_back(Rec{dst, src, bytes});
+        return 0;
+    }
+};
+
+// The pieces `d` declared on one plan in the given forms; want: the offsets of
+// the hand-written chain for the staged pieces (SIZE_MAX: not checked), want_size its end.
+static void plan_check(const std::vector<Decl>& d, bool host_in, bool host_out, const std::vector<size_t>* want = nullptr,
+                       size_t want_size = 0) {
+    const size_t N = d.size();
+    std::vector<std::vector<unsigned char>> host(N);
+    std::vector<const unsigned char*> ip(N, (const unsigned char*)0x10);
+    std::vector<unsigned char*> op(N, (unsigned char*)0x10);
+    StagePlan plan(host_in, host_out);
+    size_t scratch_room = 0;
+    for (size_t i = 0; i < N; i++) {
+        host[i].assign(d[i].bytes + 1, 0);             // (+1: an address of its own even when empty)
+        for (size_t j = 0; j < d[i].bytes; j++) host[i][j] = (unsigned char)(i * 37 + j * 11 + 1);
+        if (d[i].kind == 0) plan.in(d[i].on, &ip[i], host[i].data(), d[i].bytes, d[i].room == d[i].bytes ? 0 : d[i].room);
+        else if (d[i].kind == 1) plan.out(d[i].on, &op[i], host[i].data(), d[i].bytes, d[i].copy_back);
+        else plan.scratch(d[i].on, &op[i], d[i].bytes);
+        if (d[i].kind == 2 && d[i].on) scratch_room += align_up(d[i].room);
+    }
+    auto staged = [&](size_t i) { return d[i].on && (d[i].kind == 2 || (d[i].kind == 0 ? host_in : host_out)); };
+    auto ptr = [&](size_t i) { return d[i].kind == 0 ? ip[i] : (const unsigned char*)op[i]; };
+    if (!host_in && !host_out) CHECK(plan.size() == scratch_room);
+    if (want) CHECK(plan.size() == want_size);
+    // the buffer: a failing allocation leaves it empty, the retry succeeds
+    DevPool pool(MEM);
+    GrowBuf buf;
+    if (plan.size()) {
+        fail_in = 1;
+        CHECK(buf.reserve(pool, plan.size()) == NOMEM && !buf.p && buf.bytes == 0 && pool.count() == 0);
+    }
+    CHECK(buf.reserve(pool, plan.size()) == 0 && buf.bytes == plan.size());
+    plan.bind(buf.p);
+    const unsigned char* base = (const unsigned char*)buf.p;
+    size_t end = 0;                                     // the end of the room before
+    for (size_t i = 0; i < N; i++) {
+        if (!d[i].on) { CHECK(ptr(i) == nullptr); continue; }
+        if (!staged(i)) { CHECK(ptr(i) == host[i].data()); continue; }    // device form: the caller's pointer
+        const size_t off = (size_t)(ptr(i) - base);
+        CHECK(off % 256 == 0 && off >= end && off + d[i].room <= plan.size());
+        CHECK(off == end);                              // declaration order, nothing between the rooms
+        if (want && (*want)[i] != SIZE_MAX) CHECK(off == (*want)[i]);
+        end = off + align_up(d[i].room);
+    }
+    CHECK(end == plan.size());
+    // upload: exactly `bytes` of every staged input with bytes, in order
+    CopyLog up;
+    CHECK(plan.upload(up) == 0);
+    size_t k = 0;
+    for (size_t i = 0; i < N; i++) {
+        if (!(staged(i) && d[i].kind == 0 && d[i].bytes)) continue;
+        CHECK(k < up.recs.size());
+        if (k >= up.recs.size()) break;
+        CHECK(up.recs[k].dst == ptr(i) && up.recs[k].src == host[i].data() && up.recs[k].bytes == d[i].bytes);
+        CHECK(std::memcmp(ptr(i), host[i].data(), d[i].bytes) == 0);
+        k++;
+    }
+    CHECK(k == up.recs.size());
+    // the "kernels" write every result; download brings back the pieces that asked
+    for (size_t i = 0; i < N; i++)
+        if (staged(i) && d[i].kind == 1 && d[i].bytes) std::memset(op[i], 0xA0 + (int)i, d[i].bytes);
+    CopyLog down;
+    CHECK(plan.download(down) == 0);
+    k = 0;
+    for (size_t i = 0; i < N; i++) {
+        if (!(staged(i) && d[i].kind == 1)) continue;
+        const bool back = d[i].copy_back && d[i].bytes;
+        if (back) {
+            CHECK(k < down.recs.size());
+            if (k >= down.recs.size()) break;
+            CHECK(down.recs[k].dst == host[i].data() && down.recs[k].src == op[i] && down.recs[k].bytes == d[i].bytes);
+            k++;
+        }
+        for (size_t j = 0; j < d[i].bytes; j++)
+            CHECK(host[i][j] == (back ? (unsigned char)(0xA0 + i) : (unsigned char)(i * 37 + j * 11 + 1)));
+        CHECK(host[i][d[i].bytes] == 0);                 // nothing past the declared bytes
+    }
+    CHECK(k == down.recs.size());
+    // a copy that fails on its k-th call: that error, and no copy after it
+    for (int dir = 0; dir < 2; dir++) {
+        const size_t total = dir ? down.recs.size() : up.recs.size();
+        for (size_t f = 1; f <= total; f++) {
+            CopyLog bad;
+            bad.fail_at = (long)f;
+            CHECK((dir ? plan.download(bad) : plan.upload(bad)) == COPY_ERR && bad.recs.size() == f);
+        }
+    }
+}
+
+// sf_request_tokens' staging: the offsets as they were written before Layout
+static void token_chain(uint32_t n, uint32_t n_vals, bool has_param, bool param_off, bool want_rem, bool want_wait) {
     size_t off_fid = 0, off_cnt = align_up(off_fid + (size_t)n * 8), off_fl = align_up(off_cnt + (size_t)n * 4),
            off_ts = align_up(off_fl + n), off_tag = align_up(off_ts + (size_t)n * 8),
            off_bits = align_up(off_tag + (has_param ? n_vals : 0)),
            off_po = align_up(off_bits + (has_param ? (size_t)n_vals * 8 : 0)),
            off_st = align_up(off_po + (param_off ? ((size_t)n + 1) * 4 : 0)),
            off_rem = align_up(off_st + n), off_wt = align_up(off_rem + (size_t)n * 4), need = align_up(off_wt + (size_t)n * 4);
-    Layout L;
-    CHECK(L.take((size_t)n * 8) == off_fid); CHECK(L.take((size_t)n * 4) == off_cnt); CHECK(L.take(n) == off_fl);
-    CHECK(L.take((size_t)n * 8) == off_ts);
-    const size_t g_tag = L.take_if(has_param, n_vals), g_bits = L.take_if(has_param, (size_t)n_vals * 8);
-    const size_t g_po = L.take_if(param_off, ((size_t)n + 1) * 4);
-    if (has_param) { CHECK(g_tag == off_tag); CHECK(g_bits == off_bits); }
-    if (param_off) CHECK(g_po == off_po);
-    CHECK(L.take(n) == off_st); CHECK(L.take((size_t)n * 4) == off_rem); CHECK(L.take((size_t)n * 4) == off_wt);
-    CHECK(L.size() == need);
+    const std::vector<Decl> d = {d_in(true, (size_t)n * 8), d_in(true, (size_t)n * 4), d_in(true, n), d_in(true, (size_t)n * 8),
+                                 d_in(has_param, n_vals), d_in(has_param, (size_t)n_vals * 8),
+                                 d_in(param_off, ((size_t)n + 1) * 4),
+                                 d_out(true, n), d_out(true, (size_t)n * 4, want_rem), d_out(true, (size_t)n * 4, want_wait)};
+    const std::vector<size_t> want = {off_fid, off_cnt, off_fl, off_ts, off_tag, off_bits, off_po, off_st, off_rem, off_wt};
+    plan_check(d, true, true, &want, need);
+    for (int form = 0; form < 3; form++) plan_check(d, form & 1, form & 2);    // mixed and device forms
 }
 
-// stage_batch's host input staging as it was written before Layout
+// stage_batch's host input staging: the offsets as they were written before Layout
 static void stage_chain(uint32_t n, uint32_t arg_slots, uint32_t n_elems, bool entry_ref, bool create_ts, bool n_args,
                         bool coll, bool origin, bool context) {
     size_t need = 0;
@@ -234,25 +346,45 @@ static void stage_chain(uint32_t n, uint32_t arg_slots, uint32_t n_elems, bool e
     size_t o_eb = need; need += coll ? align_up((size_t)n_elems * 8) : 0;
     size_t o_og = need; need += origin ? align_up((size_t)n * 4) : 0;
     size_t o_cx = need; need += context ? align_up((size_t)n * 4) : 0;
-    Layout L;
-    CHECK(L.take((size_t)n * 4) == o_res); CHECK(L.take((size_t)n * 8) == o_ts); CHECK(L.take((size_t)n * 4) == o_cnt);
-    CHECK(L.take(n) == o_fl);
-    CHECK(L.take_if(entry_ref, (size_t)n * 8) == o_er);
-    CHECK(L.take_if(entry_ref && create_ts, (size_t)n * 8) == o_ct);
-    CHECK(L.take_if(n_args, n) == o_na);
-    CHECK(L.take((size_t)n * arg_slots) == o_at); CHECK(L.take((size_t)n * arg_slots * 8) == o_ab);
-    CHECK(L.take_if(coll, ((size_t)n * arg_slots + 1) * 4) == o_eo);
-    CHECK(L.take_if(coll, n_elems) == o_et); CHECK(L.take_if(coll, (size_t)n_elems * 8) == o_eb);
-    CHECK(L.take_if(origin, (size_t)n * 4) == o_og); CHECK(L.take_if(context, (size_t)n * 4) == o_cx);
-    CHECK(L.size() == need);
+    // (an array is declared off when the batch has none of it: n == 0, no slots, no elements)
+    const size_t na = (size_t)n * arg_slots;
+    const std::vector<Decl> d = {
+        d_in(n, (size_t)n * 4), d_in(n, (size_t)n * 8), d_in(n, (size_t)n * 4), d_in(n, n),
+        d_in(entry_ref && n, (size_t)n * 8), d_in(entry_ref && create_ts && n, (size_t)n * 8), d_in(n_args && n, n),
+        d_in(na, na), d_in(na, na * 8), d_in(coll, (na + 1) * 4), d_in(coll && n_elems, n_elems),
+        d_in(coll && n_elems, (size_t)n_elems * 8), d_in(origin && n, (size_t)n * 4), d_in(context && n, (size_t)n * 4)};
+    const std::vector<size_t> want = {o_res, o_ts, o_cnt, o_fl, o_er, o_ct, o_na, o_at, o_ab, o_eo, o_et, o_eb, o_og, o_cx};
+    plan_check(d, true, false, &want, need);
+    plan_check(d, false, false);
+    // the verdicts: status always, wait_ms / rule_idx when the caller has them
+    for (int m = 0; m < 4; m++) {
+        const std::vector<Decl> v = {d_out(true, n), d_out(m & 1, (size_t)n * 4), d_out(m & 2, (size_t)n * 2)};
+        plan_check(v, false, true);
+        plan_check(v, false, false);
+    }
+}
+
+// scratch in either form, a room wider than the copy, and the inline capacity
+static void plan_cases() {
+    for (uint32_t n : {0u, 1u, 255u, 256u, 257u})
+        for (int m = 0; m < 8; m++) {
+            const std::vector<Decl> d = {d_in(true, n, (size_t)n + 16), d_scratch(m & 1, (size_t)n * 4), d_out(m & 2, n, m & 4),
+                                         d_scratch(true, 16), d_in(m & 4, 0)};
+            for (int form = 0; form < 4; form++) plan_check(d, form & 1, form & 2);
+        }
+    StagePlan full(true, true);
+    char* p[StagePlan::CAP];
+    for (int i = 0; i < StagePlan::CAP; i++) full.scratch(&p[i], 1);
+    CHECK(full.size() == (size_t)StagePlan::CAP * 256);
 }
 
 static void layout_cases() {
     const uint32_t ns[] = {0, 1, 255, 256, 257};
     for (uint32_t n : ns) {
-        for (int m = 0; m < 4; m++) {
-            token_chain(n, n, m & 1, m & 2);
-            token_chain(n, 2 * n + 3, m & 1, m & 2);             // collection params: more values than requests
+        for (int m = 0; m < 16; m++) {
+            token_chain(n, n, m & 1, m & 2, m & 4, m & 8);
+            token_chain(n, 2 * n + 3, m & 1, m & 2, m & 4, m & 8);   // collection params: more values than requests
+            token_chain(n, 0, m & 1, m & 2, m & 4, m & 8);           // param arrays passed with no value
         }
         for (int m = 0; m < 64; m++)
             for (uint32_t slots : {0u, 1u, 3u})
@@ -270,6 +402,7 @@ int main() {
     cc_cases();
     dg_cases();
     layout_cases();
+    plan_cases();
     CHECK(live() == 0 && n_alloc == n_free && fail_in == 0);
     std::printf("%ld allocations, %ld frees, %d failures\n", n_alloc, n_free, failures);
     return failures ? 1 : 0;

@@ -1,7 +1,7 @@
 """Who owns device memory (sentinel_amd/csrc/sf_mem.h, sf_worksets.h), checked
 on the host: tests/mem_check.cpp runs the pool, the grow-only buffer, the
-work-set growth functions and the layout cursor on a malloc backend that fails
-the k-th allocation, under the address and undefined-behaviour sanitizers (the
+work-set growth functions, the layout cursor and the staging plan (StagePlan,
+with memcpy as its copy) on a malloc backend that fails the k-th allocation, under the address and undefined-behaviour sanitizers (the
 leak check at exit included).  Nothing is loaded into Python; the kernel headers
 the work sets come from are compiled as host code, like tests/hostsim."""
 import os

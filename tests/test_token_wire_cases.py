@@ -34,12 +34,12 @@ def test_wire_constants_match_the_source():
     ("sf_token.hip", "while (e - a > 64)", "while (e - a > 32)"),
     ("sf_token.hip", "(e - a + 63) / 64", "(e - a + 31) / 32"),
     ("sf_decide.h", "PT_MAX_PROBE = 4096", "PT_MAX_PROBE = 1024"),
-    ("sf_engine.cpp", "uint64_t pc = 1024;", "uint64_t pc = 4096;"),
-    ("sf_engine.cpp", "if (n > 255) return fail", "if (n > 254) return fail"),
+    ("sf_host_cluster.cpp", "uint64_t pc = 1024;", "uint64_t pc = 4096;"),
+    ("sf_host_cluster.cpp", "if (n > 255) return fail", "if (n > 254) return fail"),
 ])
 def test_token_drift_is_noticed(tmp_path, name, old, new):
     """The same check on a copy of the sources with one constant edited."""
-    for f in ("sf_token.h", "sf_token.hip", "sf_decide.h", "sf_engine.cpp"):
+    for f in ("sf_token.h", "sf_token.hip", "sf_decide.h", "sf_host_cluster.cpp"):
         shutil.copy(os.path.join(tc._CSRC, f), tmp_path / f)
     src = (tmp_path / name).read_text()
     assert src.count(old) == 1, (name, old)

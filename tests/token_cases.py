@@ -38,8 +38,8 @@ CL_MAXS = 16                                    # sf_token.h: largest sample_cou
 TD_T = 64                                       # sf_token.hip: segments per workgroup of k_tok_decide
 NS_NONE = 0xFF                                  # sf_token.hip: namespace key of an unlimited request
 PT_MAX_PROBE = 4096                             # sf_decide.h: probe reach of the value table
-CP_MIN_SLOTS = 1024                             # sf_engine.cpp tok_rebuild: smallest value table
-NS_MAX = 255                                    # sf_engine.cpp sf_load_namespaces
+CP_MIN_SLOTS = 1024                             # sf_host_cluster.cpp tok_rebuild: smallest value table
+NS_MAX = 255                                    # sf_host_cluster.cpp sf_load_namespaces
 SEARCH_FAN = 64                                 # k_ns_limit: `e - a > 64`, step = (e - a + 63) / 64
 
 MIRROR = dict(LIM=(LIM_S, LIM_WL, LIM_INTERVAL), CL_MAXS=CL_MAXS, TD_T=TD_T, NS_NONE=NS_NONE,
@@ -56,7 +56,7 @@ def source_constants(csrc=_CSRC):
         m = re.findall(pat, src)
         assert len(m) == 1, (pat, m)
         return m[0]
-    tok_h, tok, dec, eng = text("sf_token.h"), text("sf_token.hip"), text("sf_decide.h"), text("sf_engine.cpp")
+    tok_h, tok, dec, eng = text("sf_token.h"), text("sf_token.hip"), text("sf_decide.h"), text("sf_host_cluster.cpp")
     out = {}
     out["LIM"] = tuple(int(x) for x in one(
         tok_h, r"constexpr int LIM_S = (\d+), LIM_WL = (\d+), LIM_INTERVAL = (\d+);"))
