@@ -1055,6 +1055,175 @@ int  sf_flow_rule_order(const sf_flow_rule* rules, const sf_rule_key* keys, uint
 int  sf_param_rule_order(const sf_param_rule* rules, const sf_rule_key* keys, uint32_t n, const sf_hot_item* items,
                          uint32_t n_items, uint32_t* order, uint32_t* n_out);
 
+/* ---- API-gateway flow rules (sentinel-api-gateway-adapter-common) ----------
+ * GatewayFlowSlot (order -4000: after SystemSlot, before ParamFlowSlot) runs
+ * ParamFlowChecker.passCheck over the ParamFlowRules that GatewayRuleManager
+ * converts GatewayFlowRules into, on arguments that GatewayParamParser parses
+ * out of the request.  The engine takes all three parts:
+ *   sf_gateway_convert     the conversion (host only, no engine)
+ *   sf_load_gateway_rules  converts and keeps the result as the gateway list
+ *   sf_gateway_args        the parser, on the device: requests -> the argument
+ *                          columns of an ordinary sf_event_batch
+ * The verdicts then come from the existing submit calls.
+ *
+ * Rules.  The array is the iteration order of the Set given to
+ * GatewayRuleManager.loadRules (the caller has it; it is not re-derived).
+ *   resource_hash: getResource().hashCode().  has_item 0: paramItem null (the
+ *   fields after it are not read).  field_id: the caller's id of the request
+ *   item the rule reads (one id per header / cookie / URL-parameter name, one
+ *   for the client IP, one for Host; a REGEX rule takes an id of its own, see
+ *   below).  field_name_blank: StringUtil.isBlank(fieldName).  pattern: index
+ *   into the string table passed with the rules, SF_GW_NONE = null; an empty
+ *   string is an empty pattern (no match is applied, but the rule still gets
+ *   the "$NM" hot item).
+ * Conversion (applyGatewayRuleInternal, GatewayRuleManager.java:179-237).
+ *   Invalid rules are dropped (isValidRule / isValidParamItem :117-145).  The
+ *   item rules of a resource get the indices 0, 1, ... in array order; a rule
+ *   whose pattern is not null gets the one hot item ("$NM", String,
+ *   10,000,000).  The rules without an item all take the next index and equal
+ *   ones collapse.  The converted rules come out in the order
+ *   GatewayRuleManager holds them: the iteration order of the global
+ *   HashSet<ParamFlowRule>, then ParamFlowRuleUtil.buildParamRuleMap (which
+ *   drops what ParamFlowRuleUtil.isValidRule refuses: a negative
+ *   maxQueueingTimeoutMs under a behaviour other than RATE_LIMITER; such a
+ *   rule keeps its argument slot).  slot_of_rule[i]: the index of rule i, -1
+ *   for a dropped one.  out_desc: one per resource in order of first
+ *   appearance: n_item_slots item slots (what each reads), n_slots = that plus
+ *   one when a rule without item exists, and mode_gate (sf_gateway_args).
+ *   out_rules, out_items, slot_of_rule and out_desc hold n elements each.
+ *   SF_ERR_UNSUPPORTED: a HashMap bin would be treeified (as
+ *   sf_param_rule_order).  SF_ERR_CAPACITY: a resource with more than
+ *   SF_MAX_ARGS slots or more than SF_MAX_RULES_PER_RESOURCE converted rules.
+ *   SF_ERR_INVALID: a pattern index that is neither SF_GW_NONE nor < n_str.
+ * sf_load_gateway_rules.  The ParamFlow stage of a resource evaluates its
+ *   gateway list first, then the list of sf_load_param_rules (the two slots
+ *   are adjacent, share the entry's args and both throw ParamFlowException):
+ *   verdict SF_V_BLOCK_PARAM, rule_idx indexes the concatenation.  Each of the
+ *   two load calls replaces its own list only (n == 0 clears it); the two
+ *   lists of a resource together hold at most SF_MAX_RULES_PER_RESOURCE rules
+ *   (SF_ERR_CAPACITY).  Like sf_load_param_rules, a load waits for the batches
+ *   in flight and resets all ParameterMetric state of every resource (the
+ *   reference clears per rule: GatewayRuleManager.java:252-268; this is the
+ *   engine's one divergence in rule loading, for both calls).  A converted
+ *   rule that equals a rule of sf_load_param_rules on the same resource would
+ *   share its counters in ParameterMetric: SF_ERR_UNSUPPORTED, from whichever
+ *   load comes second.  A rule of another shard is SF_ERR_INVALID.  Without
+ *   gateway rules loaded nothing changes anywhere.
+ * sf_gateway_args.  Request i has ts_ms, count and flags (SF_EV_IN /
+ *   SF_EV_PRIO; other bits are dropped), the entries res_id / res_mode
+ *   [res_off[i], res_off[i+1]) it makes (the route first, then each matching
+ *   API name, as SentinelGatewayFilter does; matching API definitions to paths
+ *   stays with the front-end) and the request items val_field / val_str /
+ *   val_flags [val_off[i], val_off[i+1]) that are present: field id, index
+ *   into the batch's string table (str_off, bytes as in sf_rls_batch), flags
+ *   (val_flags may be NULL).  Of two items with one field id the first is used.
+ *   The entries of request i become the events ev_index[i], ev_index[i] + 1,
+ *   ... of the caller's columns (stride n_total): res_id, ts_ms, count, flags,
+ *   n_args and all SF_MAX_ARGS slots of arg_tag / arg_bits (slot-major,
+ *   arg_slots = SF_MAX_ARGS; slots from n_args on are SF_TAG_NULL, 0).  No
+ *   other position is written, so the caller fills EXITs and unrelated events
+ *   itself, except the EXITs listed in exit_pos: their entry_ref must point at
+ *   a gateway entry of this batch, whose n_args / tags / bits they get (an
+ *   EXIT carries its entry's arguments; for an EXIT of an earlier batch the
+ *   caller kept them).
+ *   Per entry (parseParameterFor, GatewayParamParser.java:51-84):
+ *     no gateway rule on the resource                       n_args 0
+ *     item rules whose resource_mode differs from the entry's res_mode, or
+ *       differ among themselves                             n_args 0 (all pass)
+ *     only rules without item                               one slot "$D"
+ *     else n_slots slots; per item slot:
+ *       item absent, or parse_strategy outside 0..4         SF_TAG_NULL
+ *       pattern null or empty                               the value
+ *       EXACT (0) / CONTAINS (3)                            the value if equal to / containing the pattern, else "$NM"
+ *       REGEX (2)                                           the value unless val_flags has SF_GW_NOMATCH (the caller
+ *                                                           evaluates the regex; two regex rules on one field take two ids)
+ *       any other match_strategy, PREFIX (1) included       the value (the reference's default: branch)
+ *     and "$D" in the last slot when a rule without item exists.
+ *   A value is (SF_TAG_STRING, sf_gateway_string_bits(its UTF-8 bytes)), FNV-1a
+ *   64; "$NM" and "$D" likewise, so a request value "$NM" equals the constant
+ *   as in Java.  Divergences: two distinct strings with equal 64-bit hashes
+ *   share a counter; values are compared as bytes, which is String.equals /
+ *   contains for well-formed UTF-8 on both sides; nothing validates UTF-8.
+ *   Hot items of ordinary param rules over these arguments carry
+ *   sf_gateway_string_bits of the String.
+ *   Errors, decided before anything is written: SF_ERR_INVALID for offsets
+ *   that do not start at 0 or decrease, a string index >= n_str, event ranges
+ *   that overlap or pass n_total, a resource of another shard, an exit_pos that
+ *   is out of range or a gateway entry or whose entry_ref is not a gateway
+ *   entry of this batch, in->mem != out->mem; SF_ERR_CAPACITY when n, the
+ *   entries, n_total or n_exit exceed max_batch or the strings hold 2^31 bytes
+ *   or more.  Runs on the engine's stream under its mutex; it reads no state
+ *   but the rule tables, so it may run while asynchronous batches are in
+ *   flight (not into columns they still read).                              */
+#define SF_GW_NONE       0xFFFFFFFFu
+#define SF_GW_NOMATCH    0x01u     /* val_flags: the caller's regex did not match */
+#define SF_GW_GATE_ANY   (-1)      /* mode_gate: no item rule, every entry gets "$D" */
+#define SF_GW_GATE_NEVER (-2)      /* mode_gate: item rules of several modes, no entry gets arguments */
+#define SF_GW_NM_COUNT   10000000  /* count of the "$NM" hot item */
+typedef struct sf_gateway_rule {
+    uint32_t resource;
+    int32_t  resource_hash;
+    int32_t  resource_mode;            /* 0 route id, 1 custom API name */
+    int32_t  grade;
+    double   count;
+    int64_t  interval_sec;
+    int32_t  control_behavior;
+    int32_t  burst;
+    int32_t  max_queueing_timeout_ms;
+    int32_t  has_item;
+    int32_t  parse_strategy;           /* 0 client IP, 1 host, 2 header, 3 URL param, 4 cookie */
+    uint32_t field_id;
+    int32_t  field_name_blank;
+    int32_t  match_strategy;           /* 0 exact, 1 prefix, 2 regex, 3 contains */
+    uint32_t pattern;
+    uint32_t pad;
+} sf_gateway_rule;
+typedef struct sf_gateway_slot {
+    uint32_t field_id;
+    int32_t  parse_strategy, match_strategy;
+    uint32_t pattern;                  /* as in the rule */
+} sf_gateway_slot;
+typedef struct sf_gateway_desc {
+    uint32_t resource;
+    uint32_t n_slots, n_item_slots;
+    int32_t  mode_gate;                /* the one resource_mode of the item rules, or SF_GW_GATE_* */
+    sf_gateway_slot slot[SF_MAX_ARGS]; /* [n_item_slots] */
+} sf_gateway_desc;
+typedef struct sf_gateway_batch {
+    uint32_t n; int32_t mem;            /* requests; SF_MEM_HOST / SF_MEM_DEVICE (all arrays) */
+    const int64_t*  ts_ms;              /* [n] */
+    const int32_t*  count;              /* [n] */
+    const uint8_t*  flags;              /* [n] */
+    const uint32_t* res_off;            /* [n+1] */
+    const uint32_t* res_id;             /* [res_off[n]] */
+    const int32_t*  res_mode;           /* [res_off[n]] */
+    const uint32_t* val_off;            /* [n+1] */
+    const uint32_t* val_field;          /* [val_off[n]] */
+    const uint32_t* val_str;            /* [val_off[n]] */
+    const uint8_t*  val_flags;          /* [val_off[n]] or NULL */
+    const uint32_t* str_off;            /* [n_str+1] byte offsets, total < 2^31 */
+    const uint8_t*  bytes;              /* UTF-8 */
+    uint32_t        n_str;
+    const uint32_t* ev_index;           /* [n] */
+} sf_gateway_batch;
+typedef struct sf_gateway_events {
+    int32_t mem; uint32_t n_total;      /* as in->mem; the length of the columns */
+    uint32_t* res_id; int64_t* ts_ms; int32_t* count; uint8_t* flags;   /* [n_total] */
+    uint8_t*  n_args;                   /* [n_total] */
+    uint8_t*  arg_tag;                  /* [SF_MAX_ARGS * n_total] */
+    uint64_t* arg_bits;                 /* [SF_MAX_ARGS * n_total] */
+    const int64_t*  entry_ref;          /* [n_total], read at exit_pos only; NULL when n_exit == 0 */
+    const uint32_t* exit_pos;           /* [n_exit] */
+    uint32_t        n_exit;
+} sf_gateway_events;
+int  sf_gateway_convert(const sf_gateway_rule* rules, uint32_t n, const uint32_t* str_off, const uint8_t* bytes,
+                        uint32_t n_str, sf_param_rule* out_rules, uint32_t* n_rules, sf_hot_item* out_items,
+                        uint32_t* n_items, int32_t* slot_of_rule, sf_gateway_desc* out_desc, uint32_t* n_desc);
+int  sf_load_gateway_rules(sf_engine* e, const sf_gateway_rule* rules, uint32_t n, const uint32_t* str_off,
+                           const uint8_t* bytes, uint32_t n_str);
+int  sf_gateway_args(sf_engine* e, const sf_gateway_batch* in, sf_gateway_events* out);
+uint64_t sf_gateway_string_bits(const uint8_t* bytes, uint32_t len);   /* host only */
+
 /* Device helpers so hosts without a GPU framework can stage HBM inputs. */
 int  sf_device_alloc(sf_engine* e, size_t bytes, void** ptr);
 int  sf_device_free(sf_engine* e, void* ptr);

@@ -51,6 +51,14 @@ final class SentinelFlowNative {
             FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS));
     static final MethodHandle AUTHORITY_MARK = fn("sf_authority_mark",
             FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, ADDRESS));
+    // GatewayRuleManager.loadRules into the engine and the request parser (the layouts and the packer:
+    // GatewayRuleTable); sf_gateway_args fills the argument columns of the batch SUBMIT then decides
+    static final MethodHandle LOAD_GATEWAY = fn("sf_load_gateway_rules",
+            FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, JAVA_INT));
+    static final MethodHandle GATEWAY_ARGS = fn("sf_gateway_args",
+            FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
+    static final MethodHandle GATEWAY_STRING_BITS = fn("sf_gateway_string_bits",
+            FunctionDescriptor.of(JAVA_LONG, ADDRESS, JAVA_INT));
     // decisions
     static final MethodHandle SUBMIT = fn("sf_submit", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
     static final MethodHandle SUBMIT_PACKED = fn("sf_submit_packed",
@@ -183,6 +191,8 @@ final class SentinelFlowNative {
             V_BLOCK_SYSTEM = 5, V_EXIT = 6, V_EXIT_IGNORED = 7, V_BLOCK_DEGRADE = 8, V_BLOCK_OTHER = 9,
             V_BLOCK_AUTHORITY = 10;
     static final int AUTHORITY_WHITE = 0, AUTHORITY_BLACK = 1;
+    static final byte GW_NOMATCH = 0x01;      // val_flags of sf_gateway_batch: the caller's regex did not match
+    static final int GW_NM_COUNT = 10000000;  // count of the "$NM" hot item of a converted gateway rule
     static final byte TOK_PRIORITIZED = 0x01, TOK_PARAM = 0x02;
     static final byte TAG_NULL = 0, TAG_INT = 1, TAG_LONG = 2, TAG_STRING = 3, TAG_DOUBLE = 4, TAG_BOOL = 5,
             TAG_OTHER = 6, TAG_BYTE = 7, TAG_SHORT = 8, TAG_FLOAT = 9, TAG_COLLECTION = 0x40;

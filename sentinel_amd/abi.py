@@ -922,3 +922,112 @@ class HostRlsResults:
         for name, _ in self.FIELDS:
             setattr(r, name, _ptr(getattr(self, name)))
         return r
+
+
+# ---- API-gateway flow rules (sf_load_gateway_rules, sf_gateway_args)
+GW_NONE = 0xFFFFFFFF             # sf_gateway_rule.pattern: null
+GW_NOMATCH = 0x01                # val_flags: the caller's regex did not match
+GW_GATE_ANY, GW_GATE_NEVER = -1, -2
+GW_NM_COUNT = 10_000_000
+
+
+class sf_gateway_rule(C.Structure):
+    _fields_ = [("resource", C.c_uint32), ("resource_hash", C.c_int32), ("resource_mode", C.c_int32),
+                ("grade", C.c_int32), ("count", C.c_double), ("interval_sec", C.c_int64),
+                ("control_behavior", C.c_int32), ("burst", C.c_int32), ("max_queueing_timeout_ms", C.c_int32),
+                ("has_item", C.c_int32), ("parse_strategy", C.c_int32), ("field_id", C.c_uint32),
+                ("field_name_blank", C.c_int32), ("match_strategy", C.c_int32), ("pattern", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
+class sf_gateway_slot(C.Structure):
+    _fields_ = [("field_id", C.c_uint32), ("parse_strategy", C.c_int32), ("match_strategy", C.c_int32),
+                ("pattern", C.c_uint32)]
+
+
+class sf_gateway_desc(C.Structure):
+    _fields_ = [("resource", C.c_uint32), ("n_slots", C.c_uint32), ("n_item_slots", C.c_uint32),
+                ("mode_gate", C.c_int32), ("slot", sf_gateway_slot * SF_MAX_ARGS)]
+
+
+class sf_gateway_batch(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("mem", C.c_int32), ("ts_ms", C.c_void_p), ("count", C.c_void_p),
+                ("flags", C.c_void_p), ("res_off", C.c_void_p), ("res_id", C.c_void_p), ("res_mode", C.c_void_p),
+                ("val_off", C.c_void_p), ("val_field", C.c_void_p), ("val_str", C.c_void_p), ("val_flags", C.c_void_p),
+                ("str_off", C.c_void_p), ("bytes", C.c_void_p), ("n_str", C.c_uint32), ("ev_index", C.c_void_p)]
+
+
+class sf_gateway_events(C.Structure):
+    _fields_ = [("mem", C.c_int32), ("n_total", C.c_uint32), ("res_id", C.c_void_p), ("ts_ms", C.c_void_p),
+                ("count", C.c_void_p), ("flags", C.c_void_p), ("n_args", C.c_void_p), ("arg_tag", C.c_void_p),
+                ("arg_bits", C.c_void_p), ("entry_ref", C.c_void_p), ("exit_pos", C.c_void_p), ("n_exit", C.c_uint32)]
+
+
+STRUCT_SIZES.update({n: C.sizeof(c) for n, c in [("sf_gateway_rule", sf_gateway_rule), ("sf_gateway_slot", sf_gateway_slot),
+                                                 ("sf_gateway_desc", sf_gateway_desc), ("sf_gateway_batch", sf_gateway_batch),
+                                                 ("sf_gateway_events", sf_gateway_events)]})
+
+
+def string_table(strings):
+    """(str_off uint32 [n+1], bytes uint8) of a list of str / bytes."""
+    raw = [s.encode("utf-8", "surrogatepass") if isinstance(s, str) else bytes(s) for s in strings]
+    off = np.zeros(len(raw) + 1, np.uint32)
+    off[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+    return off, np.frombuffer(b"".join(raw), np.uint8).copy()
+
+
+class HostGatewayBatch:
+    """Gateway requests in host memory (sf_gateway_batch): per request its
+    entries (res_id / res_mode), the request items present (val_field, val_str
+    into the string table, val_flags) and the position of its first event."""
+
+    ARRAYS = ("ts_ms", "count", "flags", "res_off", "res_id", "res_mode", "val_off", "val_field", "val_str",
+              "val_flags", "str_off", "data", "ev_index")
+    DTYPES = (np.int64, np.int32, np.uint8, np.uint32, np.uint32, np.int32, np.uint32, np.uint32, np.uint32, np.uint8,
+              np.uint32, np.uint8, np.uint32)
+
+    def __init__(self, **arrays):
+        for name, dt in zip(self.ARRAYS, self.DTYPES):
+            setattr(self, name, np.ascontiguousarray(arrays[name], dt))
+        self.n = self.ts_ms.shape[0]
+        self.n_str = self.str_off.shape[0] - 1
+        assert self.res_off.shape == self.val_off.shape == (self.n + 1,) and self.ev_index.shape == (self.n,)
+
+    def c_struct(self, ptr=None) -> sf_gateway_batch:
+        """ptr: {array name: device address} for a batch in device memory."""
+        b = sf_gateway_batch()
+        b.n, b.mem, b.n_str = self.n, MEM_HOST if ptr is None else MEM_DEVICE, self.n_str
+        for name in self.ARRAYS:
+            setattr(b, "bytes" if name == "data" else name, _ptr(getattr(self, name)) if ptr is None else ptr[name])
+        return b
+
+
+class HostGatewayEvents:
+    """The event columns sf_gateway_args fills (stride n_total), with the
+    entry_ref column and the exits that take their entry's arguments."""
+
+    COLUMNS = (("res_id", np.uint32), ("ts_ms", np.int64), ("count", np.int32), ("flags", np.uint8),
+               ("n_args", np.uint8), ("arg_tag", np.uint8), ("arg_bits", np.uint64))
+
+    def __init__(self, n_total, entry_ref=None, exit_pos=()):
+        self.n_total = int(n_total)
+        for name, dt in self.COLUMNS:
+            shape = (SF_MAX_ARGS, self.n_total) if name.startswith("arg_") else (self.n_total,)
+            setattr(self, name, np.zeros(shape, dt))
+        self.entry_ref = None if entry_ref is None else np.ascontiguousarray(entry_ref, np.int64)
+        self.exit_pos = np.ascontiguousarray(exit_pos, np.uint32)
+        assert self.entry_ref is None or self.entry_ref.shape == (self.n_total,)
+        assert not self.exit_pos.size or self.entry_ref is not None
+
+    def c_struct(self, ptr=None) -> sf_gateway_events:
+        o = sf_gateway_events()
+        o.mem, o.n_total, o.n_exit = MEM_HOST if ptr is None else MEM_DEVICE, self.n_total, self.exit_pos.size
+        for name in [c for c, _ in self.COLUMNS] + ["entry_ref", "exit_pos"]:
+            a = getattr(self, name)
+            setattr(o, name, None if a is None else (_ptr(a) if ptr is None else ptr[name]))
+        return o
+
+    def batch(self, create_ts=None, **kw) -> HostBatch:
+        """The columns as a HostBatch for the submit calls."""
+        return HostBatch(self.res_id, self.ts_ms, self.count, self.flags, entry_ref=self.entry_ref, create_ts=create_ts,
+                         arg_tag=self.arg_tag, arg_bits=self.arg_bits, n_args=self.n_args, **kw)

@@ -659,36 +659,63 @@ int sf_load_flow_rules(sf_engine* e, const sf_flow_rule* rules, uint32_t n) {
     return SF_OK;
 }
 
-int sf_load_param_rules(sf_engine* e, const sf_param_rule* rules, uint32_t n, const sf_hot_item* items,
-                        uint32_t n_items) {
-    if (!e || (n && !rules) || (n_items && !items)) return fail(SF_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    SF_TRY(drain(e));   // pending batches were sorted under the old rules
-    std::vector<uint32_t> counts(e->R + 1, 0), loc(n);
-    for (uint32_t i = 0; i < n; i++) {
-        if (!local_of(e, rules[i].resource, &loc[i])) return fail(SF_ERR_INVALID, "rule resource outside this shard");
-        if ((uint64_t)rules[i].item_offset + rules[i].item_count > n_items) return fail(SF_ERR_INVALID, "hot item range");
-        if (++counts[loc[i]] > SF_MAX_RULES_PER_RESOURCE)
-            return fail(SF_ERR_UNSUPPORTED, "more than SF_MAX_RULES_PER_RESOURCE param rules on one resource");
+// ParamFlowRule.equals of two loaded rules of one resource (their item lists as loaded)
+static bool same_param_rule(const sf_param_rule& a, const sf_hot_item* ia, const sf_param_rule& b, const sf_hot_item* ib) {
+    auto same_double = [](double x, double y) { return (x != x && y != y) || std::memcmp(&x, &y, 8) == 0; };
+    if (!(a.resource == b.resource && a.grade == b.grade && a.param_idx == b.param_idx && same_double(a.count, b.count) &&
+          a.control_behavior == b.control_behavior && a.max_queueing_time_ms == b.max_queueing_time_ms &&
+          a.burst_count == b.burst_count && a.duration_in_sec == b.duration_in_sec && a.item_count == b.item_count))
+        return false;
+    for (uint32_t t = 0; t < a.item_count; t++) {
+        const sf_hot_item &x = ia[a.item_offset + t], &y = ib[b.item_offset + t];
+        if (x.tag != y.tag || x.bits != y.bits || x.count != y.count) return false;
     }
+    return true;
+}
+
+// The ParamFlow tables of the device from the two lists a resource's ParamFlow
+// stage walks: the gateway list (sf_load_gateway_rules; GatewayFlowSlot, order
+// -4000) first, then the list of sf_load_param_rules (ParamFlowSlot, -3000).
+// Nothing is changed before both lists are checked; the caller holds e->mu
+// and has drained, and keeps the host copies of the lists.
+extern "C++" int install_param_rules(sf_engine* e, const std::vector<sf_param_rule>& gw, const std::vector<sf_hot_item>& gwi,
+                                     const sf_param_rule* rules, uint32_t n, const sf_hot_item* items, uint32_t n_items) {
+    const uint32_t ng = (uint32_t)gw.size(), ngi = (uint32_t)gwi.size(), nt = ng + n;
+    std::vector<uint32_t> counts(e->R + 1, 0), loc(nt);
+    for (uint32_t i = 0; i < nt; i++) {
+        const sf_param_rule& r = i < ng ? gw[i] : rules[i - ng];
+        if (!local_of(e, r.resource, &loc[i])) return fail(SF_ERR_INVALID, "rule resource outside this shard");
+        if (i >= ng && (uint64_t)r.item_offset + r.item_count > n_items) return fail(SF_ERR_INVALID, "hot item range");
+        if (++counts[loc[i]] > SF_MAX_RULES_PER_RESOURCE)
+            return ng ? fail(SF_ERR_CAPACITY, "more than SF_MAX_RULES_PER_RESOURCE gateway and param rules on one resource")
+                      : fail(SF_ERR_UNSUPPORTED, "more than SF_MAX_RULES_PER_RESOURCE param rules on one resource");
+    }
+    for (uint32_t i = 0; i < ng; i++)
+        for (uint32_t j = 0; j < n; j++)
+            if (same_param_rule(gw[i], gwi.data(), rules[j], items))
+                return fail(SF_ERR_UNSUPPORTED, "a converted gateway rule equals a param rule of its resource: "
+                                                "they would share one ParameterMetric counter");
     std::vector<uint32_t> off(e->R + 1, 0);
     for (uint32_t r = 0; r < e->R; r++) off[r + 1] = off[r] + counts[r];
     std::vector<uint32_t> fill(off.begin(), off.end() - 1);
-    std::vector<DevParamRule> dp(n);
-    for (uint32_t i = 0; i < n; i++) {
-        const sf_param_rule& r = rules[i];
-        DevParamRule d = make_dev_param_rule(r, (int32_t)i);
+    std::vector<DevParamRule> dp(nt);
+    for (uint32_t i = 0; i < nt; i++) {                        // (the gateway rules of a resource come first)
+        DevParamRule d = i < ng ? make_dev_param_rule(gw[i], -1 - (int32_t)i) : make_dev_param_rule(rules[i - ng], (int32_t)(i - ng));
+        if (i >= ng) d.item_off += (int32_t)ngi;
         dp[fill[loc[i]]++] = d;
     }
-    std::vector<DevHotItem> di(n_items);
-    for (uint32_t i = 0; i < n_items; i++) { di[i].bits = items[i].bits; di[i].count = items[i].count; di[i].tag = items[i].tag; }
-    e->n_prule = n;
-    e->st.n_prule = n;
+    std::vector<DevHotItem> di(ngi + n_items);
+    for (uint32_t i = 0; i < ngi + n_items; i++) {
+        const sf_hot_item& it = i < ngi ? gwi[i] : items[i - ngi];
+        di[i].bits = it.bits; di[i].count = it.count; di[i].tag = it.tag;
+    }
+    e->n_prule = nt;
+    e->st.n_prule = nt;
     e->pool.release_all(e->st.prules, e->st.items);
     SF_TRY(e->pool.alloc(&e->st.prules, std::max<size_t>(1, dp.size()) * sizeof(DevParamRule)));
     SF_TRY(e->pool.alloc(&e->st.items, std::max<size_t>(1, di.size()) * sizeof(DevHotItem)));
-    if (n) HIP_TRY(hipMemcpyAsync(e->st.prules, dp.data(), dp.size() * sizeof(DevParamRule), hipMemcpyHostToDevice, e->stream));
-    if (n_items) HIP_TRY(hipMemcpyAsync((void*)e->st.items, di.data(), di.size() * sizeof(DevHotItem), hipMemcpyHostToDevice, e->stream));
+    if (nt) HIP_TRY(hipMemcpyAsync(e->st.prules, dp.data(), dp.size() * sizeof(DevParamRule), hipMemcpyHostToDevice, e->stream));
+    if (!di.empty()) HIP_TRY(hipMemcpyAsync((void*)e->st.items, di.data(), di.size() * sizeof(DevHotItem), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync((void*)e->st.prule_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, e->stream));
     // a rule reload drops all ParameterMetric state (new ParameterMetric per resource)
     HIP_TRY(hipMemsetAsync(e->st.pm_init, 0, e->R, e->stream));
@@ -702,6 +729,17 @@ int sf_load_param_rules(sf_engine* e, const sf_param_rule* rules, uint32_t n, co
     e->p_kmax = 2ull * kmax;
     HIP_TRY(launch_rdesc(e->st, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return SF_OK;
+}
+
+int sf_load_param_rules(sf_engine* e, const sf_param_rule* rules, uint32_t n, const sf_hot_item* items,
+                        uint32_t n_items) {
+    if (!e || (n && !rules) || (n_items && !items)) return fail(SF_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    SF_TRY(drain(e));   // pending batches were sorted under the old rules
+    SF_TRY(install_param_rules(e, e->gw.rules, e->gw.items, rules, n, items, n_items));
+    e->host_prules.assign(rules, rules + n);
+    e->host_pitems.assign(items, items + n_items);
     return SF_OK;
 }
 

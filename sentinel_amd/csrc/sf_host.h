@@ -5,6 +5,7 @@
 //                        the SystemRule rounds, the read-backs, comm, utilities
 //   sf_host_cluster.cpp  token server, wire framing, RLS, concurrency tokens
 //   sf_host_degrade.cpp  DegradeSlot circuit breakers
+//   sf_host_gateway.cpp  API-gateway flow rules: the gateway list, the request parser
 //   sf_host_report.cpp   metric snapshot and metrics.log
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,6 +25,7 @@
 #include "sf_concur.h"
 #include "sf_wire.h"
 #include "sf_rls.h"
+#include "sf_gateway.h"
 #include "sf_degrade.h"
 #include "sf_mem.h"
 #include "sf_worksets.h"
@@ -103,6 +105,16 @@ struct RlsHost {
     uint32_t* len = nullptr;                             // [3] table lengths of a device-memory batch
     uint32_t wave_min = RLS_WAVE_MIN;                    // diagnostics (SF_RLS_WAVE=0): every segment on the lane route
     sf_rls_stats stats{};
+};
+
+// API-gateway flow rules (sf_gateway.hip): the converted rules (the gateway list
+// of the ParamFlow stage) and the parser's tables, in the engine's pool
+struct GwHost {
+    GwTables t{};                                        // t.of null: no gateway rule loaded
+    std::vector<sf_param_rule> rules;                    // the gateway list (sf_gateway_convert's order)
+    std::vector<sf_hot_item> items;
+    GrowBuf stage, own;                                  // sf_gateway_args staging; [n_total] entry of an event position
+    uint32_t* len = nullptr;                             // [8]: table lengths of a device-memory batch, a zero, the error word
 };
 
 // DegradeSlot circuit breakers (sf_degrade.hip)
@@ -234,7 +246,9 @@ struct sf_engine {
     uint8_t* sys_mask = nullptr;    // [max_batch] planner verdicts (sf_system.h)
     // rules
     std::vector<uint32_t> flow_pos;        // loaded valid rule index -> CSR position
-    uint32_t n_flow = 0, n_prule = 0;
+    uint32_t n_flow = 0, n_prule = 0;      // n_prule: both lists of the ParamFlow stage
+    std::vector<sf_param_rule> host_prules;    // the list of sf_load_param_rules (the gateway list: gw.rules)
+    std::vector<sf_hot_item> host_pitems;
     AuthTables auth{};                     // AuthorityRule tables in `pool` (auth.of null: no rule loaded)
     // the exact ParamFlow table's fill (param_reserve): inserts counted on the
     // device (st.pins), as of the last drain; upper bound of the inserts of
@@ -250,6 +264,7 @@ struct sf_engine {
     TokHost tok;
     CcHost cc;
     RlsHost rls;
+    GwHost gw;
     DgHost dg;
     ReportHost rep;
     SxHost sx;
@@ -279,3 +294,6 @@ int en_fence(sf_engine* e);
 int local_of(const sf_engine* e, uint32_t res, uint32_t* l);
 // the slot's effective-flags array of the AuthorityRule mark pass
 int slot_aflags(sf_engine* e, Slot& sl);
+// the device's ParamFlow tables from the gateway list and the list of sf_load_param_rules (drained)
+int install_param_rules(sf_engine* e, const std::vector<sf_param_rule>& gw, const std::vector<sf_hot_item>& gwi,
+                        const sf_param_rule* rules, uint32_t n, const sf_hot_item* items, uint32_t n_items);

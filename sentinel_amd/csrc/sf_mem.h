@@ -124,7 +124,8 @@ private:
 // the pointer the kernels read.  A host-form array gets room in the staging
 // buffer (Layout's offsets, in declaration order) and a copy; a device-form
 // array is read or written in place: its pointer is the caller's, it takes no
-// room and no copy.  The input and the result form are independent.  `on`
+// room and no copy.  The input and the result form are independent.  An
+// inout array (result form) is copied both ways.  `on`
 // false: the pointer is null, no room, no copy, in either form.
 //   size()   the room to reserve (the site decides when its buffer may move)
 //   bind()   every staged pointer = base + its offset
@@ -151,6 +152,12 @@ public:
         else if (!host_out_) *dev = (T*)dst;
         else add(dev, set<T>, bytes, dst, bytes, copy_back ? DOWN : NONE);
     }
+    // an array the kernels update in place (the result form): copied up, and back when asked
+    template <class T> void inout(bool on, T** dev, void* host, size_t bytes) {
+        if (!on) *dev = nullptr;
+        else if (!host_out_) *dev = (T*)host;
+        else add(dev, set<T>, bytes, host, bytes, BOTH);
+    }
     // device-only room, in either form
     template <class T> void scratch(bool on, T** dev, size_t bytes) {
         if (!on) *dev = nullptr;
@@ -165,17 +172,17 @@ public:
     }
     template <class F> int upload(F&& copy) const {
         for (int i = 0; i < n_; i++)
-            if (e_[i].dir == UP && e_[i].bytes) SF_TRY(copy((void*)(base_ + e_[i].off), (const void*)e_[i].host, e_[i].bytes));
+            if ((e_[i].dir == UP || e_[i].dir == BOTH) && e_[i].bytes) SF_TRY(copy((void*)(base_ + e_[i].off), (const void*)e_[i].host, e_[i].bytes));
         return 0;
     }
     template <class F> int download(F&& copy) const {
         for (int i = 0; i < n_; i++)
-            if (e_[i].dir == DOWN && e_[i].bytes) SF_TRY(copy(e_[i].host, (const void*)(base_ + e_[i].off), e_[i].bytes));
+            if ((e_[i].dir == DOWN || e_[i].dir == BOTH) && e_[i].bytes) SF_TRY(copy(e_[i].host, (const void*)(base_ + e_[i].off), e_[i].bytes));
         return 0;
     }
 
 private:
-    enum Dir : unsigned char { NONE, UP, DOWN };
+    enum Dir : unsigned char { NONE, UP, DOWN, BOTH };
     struct Piece { void* slot; void (*set)(void*, char*); size_t off; void* host; size_t bytes; Dir dir; };
     template <class T> static void set(void* slot, char* p) { *(T**)slot = (T*)p; }
     void add(void* slot, void (*st)(void*, char*), size_t room, void* host, size_t bytes, Dir dir) {

@@ -10,6 +10,11 @@
 // A rule that fails first is the one that blocks, and an earlier passing
 // ParamFlow rule has already consumed tokens, so this order is part of the
 // decisions (SURVEY.md §7 hard part 5).
+//
+// sf_gateway_convert restates GatewayRuleManager.applyGatewayRuleInternal
+// (sentinel-api-gateway-adapter-common, rule/GatewayRuleManager.java:179-237)
+// on top of the same machinery: GatewayFlowRules become ParamFlowRules in one
+// global HashSet, whose iteration order feeds buildParamRuleMap.
 #include <algorithm>
 #include <cstring>
 #include <map>
@@ -17,6 +22,7 @@
 #include <vector>
 
 #include "sf_decide.h"
+#include "sf_gateway.h"
 
 namespace {
 
@@ -144,6 +150,23 @@ int rule_order(const R* rules, const sf_rule_key* keys, uint32_t n, uint32_t* ou
     return SF_OK;
 }
 
+// ParamFlowRuleUtil.isValidRule (ParamFlowRuleUtil.java:46-52); local rules (checkCluster: true)
+bool valid_param_rule(const sf_param_rule& r) {
+    return r.count >= 0 && r.grade >= 0 && r.burst_count >= 0 && r.control_behavior >= 0 &&
+           r.duration_in_sec > 0 && r.max_queueing_time_ms >= 0;
+}
+int unsorted(const sf_param_rule&, const sf_rule_key&, const sf_param_rule&, const sf_rule_key&) { return 0; }
+
+constexpr int32_t java_hash(const char* s) {                   // String.hashCode of an ASCII literal
+    uint32_t h = 0;
+    for (; *s; s++) h = 31u * h + (uint8_t)*s;
+    return (int32_t)h;
+}
+// ParamFlowItem.hashCode (ParamFlowItem.java:86-91) of generateNonMatchPassParamItem():
+// object "$NM", count Integer 10,000,000, classType String.class.getName()
+constexpr int32_t GW_NM_ITEM_HASH =
+    (int32_t)(((uint32_t)java_hash("$NM") * 31u + (uint32_t)SF_GW_NM_COUNT) * 31u + (uint32_t)java_hash("java.lang.String"));
+
 }  // namespace
 
 extern "C" {
@@ -172,13 +195,121 @@ int sf_param_rule_order(const sf_param_rule* rules, const sf_rule_key* keys, uin
         }
         return true;
     };
-    // ParamFlowRuleUtil.isValidRule (ParamFlowRuleUtil.java:46-52); local rules (checkCluster: true)
-    auto valid = [](const sf_param_rule& r) {
-        return r.count >= 0 && r.grade >= 0 && r.burst_count >= 0 && r.control_behavior >= 0 &&
-               r.duration_in_sec > 0 && r.max_queueing_time_ms >= 0;
+    return rule_order(rules, keys, n, order, n_out, valid_param_rule, param_hash, eq, unsorted);
+}
+
+// GatewayRuleManager.applyGatewayRuleInternal (GatewayRuleManager.java:179-237).
+int sf_gateway_convert(const sf_gateway_rule* rules, uint32_t n, const uint32_t* str_off, const uint8_t* bytes,
+                       uint32_t n_str, sf_param_rule* out_rules, uint32_t* n_rules, sf_hot_item* out_items,
+                       uint32_t* n_items, int32_t* slot_of_rule, sf_gateway_desc* out_desc, uint32_t* n_desc) {
+    (void)bytes;                                               // only a pattern's emptiness matters here
+    if (!n_rules || !n_items || !n_desc || (n && (!rules || !out_rules || !out_items || !slot_of_rule || !out_desc)) ||
+        (n_str && !str_off))
+        return SF_ERR_INVALID;
+    struct Res { uint32_t desc; bool non_item = false; uint32_t first_non_item = 0; };
+    std::map<uint32_t, Res> by_res;
+    std::vector<sf_gateway_desc> descs;
+    std::vector<sf_param_rule> set;                            // the global HashSet<ParamFlowRule>, in insertion order
+    std::vector<sf_rule_key> keys;
+    std::vector<uint8_t> hot;                                  // set[k] has the "$NM" item
+    auto same = [&](size_t k, const sf_param_rule& p, bool h) {
+        const sf_param_rule& q = set[k];
+        return q.resource == p.resource && q.grade == p.grade && q.param_idx == p.param_idx &&
+               same_double(q.count, p.count) && q.control_behavior == p.control_behavior &&
+               q.max_queueing_time_ms == p.max_queueing_time_ms && q.burst_count == p.burst_count &&
+               q.duration_in_sec == p.duration_in_sec && (hot[k] != 0) == h;
     };
-    auto unsorted = [](const sf_param_rule&, const sf_rule_key&, const sf_param_rule&, const sf_rule_key&) { return 0; };
-    return rule_order(rules, keys, n, order, n_out, valid, param_hash, eq, unsorted);
+    // applyToParamRule / applyNonParamToParamRule (GatewayRuleConverter.java:49-86); false: an equal rule is in the set
+    auto add = [&](const sf_gateway_rule& r, int32_t idx, bool h) {
+        sf_param_rule p{};
+        p.resource = r.resource; p.grade = r.grade; p.param_idx = idx; p.control_behavior = r.control_behavior;
+        p.count = r.count; p.max_queueing_time_ms = r.max_queueing_timeout_ms; p.burst_count = r.burst;
+        p.duration_in_sec = r.interval_sec;
+        for (size_t k = 0; k < set.size(); k++)
+            if (same(k, p, h)) return false;
+        sf_rule_key key{};
+        key.resource_hash = r.resource_hash;
+        key.extra_hash = h ? mix(1, GW_NM_ITEM_HASH) : 1;      // List.hashCode of the one item / of no item
+        set.push_back(p); keys.push_back(key); hot.push_back(h);
+        return true;
+    };
+    std::vector<uint32_t> later;                               // rules without item, handled after the loop
+    for (uint32_t i = 0; i < n; i++) {
+        const sf_gateway_rule& r = rules[i];
+        slot_of_rule[i] = -1;
+        const bool item = r.has_item != 0;
+        if (item && r.pattern != SF_GW_NONE && r.pattern >= n_str) return SF_ERR_INVALID;
+        const bool pat_null = !item || r.pattern == SF_GW_NONE;
+        const bool pat_empty = pat_null || str_off[r.pattern + 1] == str_off[r.pattern];
+        if (!gw_valid_rule(r.resource_mode, r.grade, r.count, r.burst, r.control_behavior, r.max_queueing_timeout_ms,
+                           r.interval_sec, item, r.parse_strategy, r.field_name_blank != 0, pat_empty, r.match_strategy))
+            continue;
+        auto it = by_res.find(r.resource);
+        if (it == by_res.end()) {
+            sf_gateway_desc d{};
+            d.resource = r.resource; d.mode_gate = SF_GW_GATE_ANY;
+            it = by_res.emplace(r.resource, Res{(uint32_t)descs.size()}).first;
+            descs.push_back(d);
+        }
+        if (!item) {
+            if (!it->second.non_item) { it->second.non_item = true; it->second.first_non_item = i; }
+            later.push_back(i);
+            continue;
+        }
+        sf_gateway_desc& d = descs[it->second.desc];
+        if (d.n_item_slots >= SF_MAX_ARGS) return SF_ERR_CAPACITY;
+        add(r, (int32_t)d.n_item_slots, !pat_null);           // (a fresh index: never equal to a rule in the set)
+        d.slot[d.n_item_slots] = sf_gateway_slot{r.field_id, r.parse_strategy, r.match_strategy, r.pattern};
+        slot_of_rule[i] = (int32_t)d.n_item_slots++;
+        // predSet of parseParameterFor: one mode for all item rules, or no entry ever gets arguments
+        if (d.mode_gate == SF_GW_GATE_ANY) d.mode_gate = r.resource_mode;
+        else if (d.mode_gate != r.resource_mode) d.mode_gate = SF_GW_GATE_NEVER;
+    }
+    // noParamMap: resource by resource (which resource comes first does not reach a resource's own order)
+    std::stable_sort(later.begin(), later.end(), [&](uint32_t a, uint32_t b) {
+        return by_res[rules[a].resource].first_non_item < by_res[rules[b].resource].first_non_item;
+    });
+    for (uint32_t i : later) {                                 // always the same index (the last position)
+        const sf_gateway_desc& d = descs[by_res[rules[i].resource].desc];
+        add(rules[i], (int32_t)d.n_item_slots, false);
+        slot_of_rule[i] = (int32_t)d.n_item_slots;
+    }
+    for (auto& kv : by_res) {
+        sf_gateway_desc& d = descs[kv.second.desc];
+        d.n_slots = d.n_item_slots + (kv.second.non_item ? 1 : 0);
+        if (d.n_slots > SF_MAX_ARGS) return SF_ERR_CAPACITY;
+    }
+    // new ArrayList<>(paramFlowRules): the global set's iteration order, then buildParamRuleMap
+    std::vector<int32_t> hs(set.size());
+    for (size_t k = 0; k < set.size(); k++) hs[k] = param_hash(set[k], keys[k]);
+    std::vector<uint32_t> glob;
+    if (!hashset_order(hs, glob)) return SF_ERR_UNSUPPORTED;
+    std::vector<sf_param_rule> lst(set.size());
+    std::vector<sf_rule_key> lkeys(set.size());
+    std::vector<uint8_t> lhot(set.size());
+    for (size_t k = 0; k < glob.size(); k++) { lst[k] = set[glob[k]]; lkeys[k] = keys[glob[k]]; lhot[k] = hot[glob[k]]; }
+    std::vector<uint32_t> order(set.size() + 1);
+    uint32_t m = 0;
+    auto eq = [](const sf_param_rule&, const sf_rule_key&, const sf_param_rule&, const sf_rule_key&) { return false; };
+    const int rc = rule_order(lst.data(), lkeys.data(), (uint32_t)lst.size(), order.data(), &m, valid_param_rule, param_hash,
+                              eq, unsorted);
+    if (rc != SF_OK) return rc;
+    std::map<uint32_t, uint32_t> per_res;
+    uint32_t ni = 0;
+    for (uint32_t k = 0; k < m; k++) {
+        sf_param_rule p = lst[order[k]];
+        if (++per_res[p.resource] > SF_MAX_RULES_PER_RESOURCE) return SF_ERR_CAPACITY;
+        if (lhot[order[k]]) {                                  // generateNonMatchPassParamItem
+            p.item_offset = ni; p.item_count = 1;
+            sf_hot_item it{};
+            it.tag = SF_TAG_STRING; it.count = SF_GW_NM_COUNT; it.bits = GW_BITS_NM;
+            out_items[ni++] = it;
+        }
+        out_rules[k] = p;
+    }
+    for (size_t k = 0; k < descs.size(); k++) out_desc[k] = descs[k];
+    *n_rules = m; *n_items = ni; *n_desc = (uint32_t)descs.size();
+    return SF_OK;
 }
 
 }  // extern "C"

@@ -90,6 +90,12 @@ def _declare(L):
         f("sf_request_rls", I, P, C.POINTER(abi.sf_rls_batch), C.POINTER(abi.sf_rls_results))
         f("sf_rls_get_stats", I, P, C.POINTER(abi.sf_rls_stats))
         f("sf_rls_flow_id", C.c_int64, C.c_char_p, U32)
+    if hasattr(L, "sf_gateway_args"):      # (absent from an older tree's library)
+        f("sf_gateway_convert", I, C.POINTER(abi.sf_gateway_rule), U32, P, P, U32, C.POINTER(abi.sf_param_rule),
+          C.POINTER(U32), C.POINTER(abi.sf_hot_item), C.POINTER(U32), P, C.POINTER(abi.sf_gateway_desc), C.POINTER(U32))
+        f("sf_load_gateway_rules", I, P, C.POINTER(abi.sf_gateway_rule), U32, P, P, U32)
+        f("sf_gateway_args", I, P, C.POINTER(abi.sf_gateway_batch), C.POINTER(abi.sf_gateway_events))
+        f("sf_gateway_string_bits", C.c_uint64, C.c_char_p, U32)
     f("sf_comm_unique_id", I, C.c_char_p, C.c_size_t)
     f("sf_comm_init", I, P, I, I, C.c_char_p, C.c_size_t)
     f("sf_entry_node_allreduce", I, P, C.POINTER(abi.sf_node_state))
@@ -178,6 +184,37 @@ def rls_flow_id(key) -> int:
     if v == -(1 << 63):
         raise ValueError("ill-formed UTF-8")
     return v
+
+
+def gateway_string_bits(value) -> int:
+    """arg_bits of a String argument parsed by gateway_args (str, or UTF-8 bytes):
+    FNV-1a 64 of the bytes (sf_gateway_string_bits, host only)."""
+    raw = value.encode("utf-8", "surrogatepass") if isinstance(value, str) else bytes(value)
+    return int(lib().sf_gateway_string_bits(raw, len(raw)))
+
+
+def gateway_convert(rules, patterns=()):
+    """GatewayRuleManager's conversion of ``rules`` (sf_gateway_rule, in the
+    iteration order of the loaded Set; ``pattern`` indexes ``patterns``):
+    (converted sf_param_rules in the manager's order, their hot items,
+    slot_of_rule int32 [n], the per-resource sf_gateway_descs).  Host only."""
+    rules = list(rules)
+    n = len(rules)
+    off, data = abi.string_table(list(patterns))
+    pr, it, desc = ((cls * max(1, n))() for cls in (abi.sf_param_rule, abi.sf_hot_item, abi.sf_gateway_desc))
+    slot = np.full(max(n, 1), -1, np.int32)
+    n_pr, n_it, n_d = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    _check_host(lib().sf_gateway_convert(abi.rules_array(abi.sf_gateway_rule, rules), n, off.ctypes.data,
+                                         data.ctypes.data if data.size else None, len(patterns), pr, C.byref(n_pr), it,
+                                         C.byref(n_it), slot.ctypes.data, desc, C.byref(n_d)))
+    return ([pr[k] for k in range(n_pr.value)], [it[k] for k in range(n_it.value)], slot[:n].copy(),
+            [desc[k] for k in range(n_d.value)])
+
+
+def _check_host(rc):
+    """A host-only call: it sets no error text."""
+    if rc != 0:
+        raise EngineError(rc, "host-only call failed")
 
 
 def comm_unique_id() -> bytes:
@@ -389,6 +426,44 @@ class FlowEngine:
         """sf_authority_mark on HBM arrays (``out``: uint8 [n])."""
         _check(lib().sf_authority_mark(self.h, res_id.ptr, None if origin is None else origin.ptr, flags.ptr,
                                        int(np.prod(res_id.shape)), abi.MEM_DEVICE, out.ptr))
+
+    # ---- API-gateway flow rules (GatewayFlowSlot; batches from sentinel_amd.gateway.pack_requests)
+    def load_gateway_rules(self, rules, patterns=()):
+        """GatewayRuleManager.loadRules: ``rules`` = sf_gateway_rule in the
+        iteration order of the Set, ``patterns`` the strings their ``pattern``
+        indexes; an empty list clears the gateway list."""
+        rules = list(rules)
+        off, data = abi.string_table(list(patterns))
+        _check(lib().sf_load_gateway_rules(self.h, abi.rules_array(abi.sf_gateway_rule, rules), len(rules),
+                                           off.ctypes.data, data.ctypes.data if data.size else None, len(patterns)))
+
+    def gateway_args(self, batch: abi.HostGatewayBatch, events: abi.HostGatewayEvents, device: bool = False):
+        """sf_gateway_args: the entries of ``batch`` written into the columns of
+        ``events`` (in place).  device=True: every array lives in device memory
+        for the call (the columns are copied up and back)."""
+        if not device:
+            b, o = batch.c_struct(), events.c_struct()
+            _check(lib().sf_gateway_args(self.h, C.byref(b), C.byref(o)))
+            return events
+        bufs = {}
+        try:
+            for name in batch.ARRAYS:
+                bufs[name] = DeviceArray(self, getattr(batch, name))
+            cols = [c for c, _ in events.COLUMNS]
+            for name in cols + ["entry_ref", "exit_pos"]:
+                if getattr(events, name) is not None:
+                    bufs["out:" + name] = DeviceArray(self, getattr(events, name))
+            b = batch.c_struct({k: v.ptr for k, v in bufs.items()})
+            o = events.c_struct({k[4:]: v.ptr for k, v in bufs.items() if k.startswith("out:")})
+            try:
+                _check(lib().sf_gateway_args(self.h, C.byref(b), C.byref(o)))
+            finally:                       # (after a refused call too: the columns as the device holds them)
+                for name in cols:
+                    getattr(events, name)[...] = bufs["out:" + name].numpy()
+        finally:
+            for v in bufs.values():
+                v.free()
+        return events
 
     def submit(self, batch: abi.HostBatch, out: abi.HostVerdicts = None) -> abi.HostVerdicts:
         out = abi.HostVerdicts(batch.n) if out is None else out
