@@ -76,13 +76,8 @@ static int work_fill(sf_engine* e, Work& w, DevPool& m) {
     SF_TRY(m.alloc(&w.s_eref, nz(N * 8))); SF_TRY(m.alloc(&w.s_cts, nz(N * 8)));
     SF_TRY(m.alloc(&w.s_nargs, nz(N))); SF_TRY(m.alloc(&w.s_atag, nz(N * SF_MAX_ARGS))); SF_TRY(m.alloc(&w.s_abits, nz(N * SF_MAX_ARGS * 8)));
     SF_TRY(m.alloc(&w.v_status, nz(N))); SF_TRY(m.alloc(&w.v_wait, nz(N * 4))); SF_TRY(m.alloc(&w.v_rule, nz(N * 2)));
-    {
-        hipError_t he = query_temp_bytes((uint32_t)N, &w.sort_tmp_bytes, &w.scan_tmp_bytes, &w.pscan_tmp_bytes);
-        if (he != hipSuccess) return fail(SF_ERR_DEVICE, "scan temp size query");
-    }
+    if (query_temp_bytes((uint32_t)N, &w.sort_tmp_bytes) != hipSuccess) return fail(SF_ERR_DEVICE, "sort temp size query");
     SF_TRY(m.alloc(&w.sort_tmp, nz(w.sort_tmp_bytes)));
-    SF_TRY(m.alloc(&w.scan_tmp, nz(w.scan_tmp_bytes)));
-    SF_TRY(m.alloc(&w.pscan_tmp, nz(w.pscan_tmp_bytes)));
     // heavy / light split
     w.heavy_min = c.heavy_min_events ? c.heavy_min_events : 512;
     {
@@ -107,7 +102,7 @@ static int work_fill(sf_engine* e, Work& w, DevPool& m) {
         SF_TRY(m.alloc(&w.light_list, nz(off * 4)));
     }
     SF_TRY(m.alloc(&w.heavy_list, nz(SC * 4)));
-    SF_TRY(m.alloc(&w.counters, nz(16 * 4))); SF_TRY(m.alloc(&w.pcg, nz(N * 8))); SF_TRY(m.alloc(&w.segs_lb, nz(segs_lb_bytes((uint32_t)N))));
+    SF_TRY(m.alloc(&w.counters, nz(WC_COUNT * 4))); SF_TRY(m.alloc(&w.pcg, nz(N * 8))); SF_TRY(m.alloc(&w.segs_lb, nz(segs_lb_bytes((uint32_t)N))));
     // <= len/TILE + 2 tiles per heavy segment; a ParamFlow-only segment of more
     // than 32 events is heavy too (SM_PARAM, k_classify), whatever heavy_min
     w.fill_tile_cap = (uint32_t)(N / FILL_TILE + 2 * (N / (std::min<uint32_t>(w.heavy_min, 32u) + 1)) + 2);
@@ -270,21 +265,21 @@ static void acc_timing(sf_engine* e, Slot& sl) {
     sl.timed = false;
     hipEvent_t* ev = sl.evs;
     float a = 0, b2 = 0, c = 0, d = 0;
-    hipEventElapsedTime(&a, ev[0], ev[1]);
-    hipEventElapsedTime(&b2, ev[1], ev[2]);
-    hipEventElapsedTime(&c, ev[2], ev[3]);
-    hipEventElapsedTime(&d, ev[3], ev[4]);
+    hipEventElapsedTime(&a, ev[EV_SORT_START], ev[EV_SORTED]);
+    hipEventElapsedTime(&b2, ev[EV_SORTED], ev[EV_CLASSIFIED]);
+    hipEventElapsedTime(&c, ev[EV_CLASSIFIED], ev[EV_JOINED]);
+    hipEventElapsedTime(&d, ev[EV_JOINED], ev[EV_SCATTERED]);
     float cl = 0, li = 0, hd = 0, hf = 0, hs = 0;
-    hipEventElapsedTime(&cl, ev[10], ev[2]);
-    hipEventElapsedTime(&li, ev[5], ev[9]);
+    hipEventElapsedTime(&cl, ev[EV_CLASSIFY_START], ev[EV_CLASSIFIED]);
+    hipEventElapsedTime(&li, ev[EV_FORK], ev[EV_LIGHT_DONE]);
     if (e->st.n_window_rules) {                    // the lean walks end on stream B
         float lq = 0;
-        hipEventElapsedTime(&lq, ev[5], ev[16]);
+        hipEventElapsedTime(&lq, ev[EV_FORK], ev[EV_LEAN_DONE]);
         li = std::max(li, lq);
     }
-    hipEventElapsedTime(&hd, ev[5], ev[7]);
-    hipEventElapsedTime(&hf, ev[7], ev[8]);
-    hipEventElapsedTime(&hs, ev[11], ev[12]);
+    hipEventElapsedTime(&hd, ev[EV_FORK], ev[EV_HEAVY_DECIDED]);
+    hipEventElapsedTime(&hf, ev[EV_HEAVY_DECIDED], ev[EV_HEAVY_FILLED]);
+    hipEventElapsedTime(&hs, ev[EV_STREAM_START], ev[EV_STREAM_DONE]);
     e->stats.classify_ms += cl; e->stats.light_ms += li;
     e->stats.heavy_decide_ms += hd; e->stats.heavy_fill_ms += hf; e->stats.stream_ms += hs;
     e->stats.sort_ms += a + b2;
@@ -2164,7 +2159,7 @@ int sf_param_table_stats(sf_engine* e, uint64_t* used, uint64_t* capacity, uint3
 int sf_heavy_profile_read(sf_engine* e, sf_heavy_profile* out, uint32_t cap, uint32_t* n_out) {
     if (!e || !n_out || (cap && !out)) return fail(SF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> g(e->mu);
-    uint32_t cnt[7] = {0, 0, 0, 0, 0, 0, 0}, nseg = 0;
+    uint32_t cnt[WC_STREAM_BACK + 1] = {}, nseg = 0;       // the list lengths of Work::counters
     SF_TRY(drain(e));
     const Work& lw = e->slot[e->last].w;
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -2173,7 +2168,8 @@ int sf_heavy_profile_read(sf_engine* e, sf_heavy_profile* out, uint32_t cap, uin
     if (e->stream4) HIP_TRY(hipStreamSynchronize(e->stream4));
     HIP_TRY(hipMemcpy(cnt, lw.counters, sizeof cnt, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&nseg, lw.n_seg, 4, hipMemcpyDeviceToHost));
-    const uint32_t n1 = cnt[1] + cnt[4], n2 = cnt[5] + cnt[6];
+    const uint32_t hf = cnt[WC_HEAVY_FRONT], sf = cnt[WC_STREAM_FRONT];
+    const uint32_t n1 = hf + cnt[WC_HEAVY_BACK], n2 = sf + cnt[WC_STREAM_BACK];
     const uint32_t nh = std::min(n1 + n2, cap);
     std::vector<uint32_t> full(lw.seg_cap), full2(lw.seg_cap), list(nh), start(nseg + 1), res(nseg);
     std::vector<uint8_t> mode(nseg);
@@ -2187,11 +2183,11 @@ int sf_heavy_profile_read(sf_engine* e, sf_heavy_profile* out, uint32_t cap, uin
         HIP_TRY(hipMemcpy(ticks2.data(), lw.sticks, n2 * 8, hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i < nh; i++) {
             if (i < n1) {
-                list[i] = i < cnt[1] ? full[i] : full[lw.seg_cap - 1 - (i - cnt[1])];
+                list[i] = i < hf ? full[i] : full[lw.seg_cap - 1 - (i - hf)];
                 tk[i] = ticks[i];
             } else {
                 const uint32_t k = i - n1;
-                list[i] = k < cnt[5] ? full2[k] : full2[lw.seg_cap - 1 - (k - cnt[5])];
+                list[i] = k < sf ? full2[k] : full2[lw.seg_cap - 1 - (k - sf)];
                 tk[i] = ticks2[k];
             }
         }

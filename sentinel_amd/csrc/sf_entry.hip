@@ -356,6 +356,12 @@ __global__ void k_snapshot_total(const uint32_t* counts, const uint32_t* offsets
     *total = R ? offsets[R - 1] + counts[R - 1] : 0;
 }
 
+// scratch of launch_snapshot's scan over n resources
+hipError_t rocprim_scan_bytes(uint32_t n, size_t* bytes) {
+    return rocprim::exclusive_scan(nullptr, *bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n,
+                                   rocprim::plus<uint32_t>());
+}
+
 hipError_t launch_snapshot(const DevState& st, int64_t now, uint32_t shard_count, uint32_t shard_index,
                            uint32_t* counts, uint32_t* offsets, sf_metric_row* out, uint32_t cap, uint32_t* total,
                            void* scan_tmp, size_t scan_bytes, hipStream_t s) {

@@ -86,7 +86,8 @@ SF_HD uint8_t heavy_mode(const DevState& st, uint32_t res, uint32_t segflags, in
 
 struct HeavyCtx {
     const uint32_t* seg_start; const uint32_t* seg_res; const uint8_t* seg_mode;
-    const uint32_t* heavy_list; const uint32_t* n_heavy;  // n_heavy[0] front count, n_heavy[3] back count
+    const uint32_t* heavy_list;
+    const uint32_t* n_heavy;           // Work::counters + WC_HEAVY_FRONT: [0] front count, [WC_HEAVY_BACK - WC_HEAVY_FRONT] back count
     uint32_t seg_cap;
     const int64_t* pcg;                // inclusive prefix of entry acquireCount over the sorted batch
     Acc* acc_hw; Acc* acc_sec; const uint32_t* acc_hw_base; const uint32_t* acc_sec_base;

@@ -114,7 +114,7 @@ struct DevState {
     int64_t* last_fetch;           // [R] StatisticNode.lastFetchTime (metric snapshot)
     int64_t* last_ts;              // engine clock: last event time of the previous batch (time never goes back)
     const RDesc* rdesc;            // [R] (k_rdesc)
-    // nonzero once any prioritized entry was submitted (k_segs): only those
+    // nonzero once any prioritized entry was submitted (k_segs_out): only those
     // write borrow buckets (tryOccupyNext), so until then every borrow bucket is
     // the initial empty one and the light lanes need not read it
     int32_t* prio_seen;
@@ -207,6 +207,25 @@ __host__ __device__ inline int light_class(uint32_t len) {
 #endif
 constexpr uint32_t FILL_TILE = SF_FILL_TILE;             // events per k_heavy_fill tile (256 threads x 8)
 
+// Slots of Work::counters, cleared by launch_classify and filled by k_classify
+// (WC_STREAM_NEXT: by k_heavy_stream).  The heavy and stream lists grow from
+// both ends: long-running segments from the front, the rest from the back.
+enum WorkCounter : uint32_t {
+    WC_LIGHT = 0,          // light segments (not kept: Work::lcounts has them per length class)
+    WC_HEAVY_FRONT = 1,    // heavy_list entries from the front (generic, or more than 65536 events)
+    WC_ACC_HW = 2,         // acc_hw slots handed out (windows of the heavy segments)
+    WC_ACC_SEC = 3,        // acc_sec slots handed out (seconds of the heavy segments)
+    WC_HEAVY_BACK = 4,     // heavy_list entries from the back
+    WC_STREAM_FRONT = 5,   // stream_list entries from the front (more than 65536 events)
+    WC_STREAM_BACK = 6,    // stream_list entries from the back (directly after WC_STREAM_FRONT: StreamCtx::n_list)
+    WC_STREAM_NEXT = 7,    // k_heavy_stream's work queue head
+    WC_SHORT = 8,          // short generic light segments (front of class 0's light_list region)
+    WC_SHORT_QPS = 9,      // short lean QPS light segments (its back; directly after WC_SHORT: k_classify, n_short)
+    WC_XW_LIST = 12,       // xw_list entries (the wave walk's segments)
+    WC_COUNT = 16
+};
+static_assert(WC_STREAM_BACK == WC_STREAM_FRONT + 1 && WC_SHORT_QPS == WC_SHORT + 1, "adjacent counter pairs");
+
 // Sorted-order working buffers of one batch.
 struct Work {
     uint32_t n;
@@ -222,16 +241,15 @@ struct Work {
     uint8_t* s_nargs; uint8_t* s_atag; uint64_t* s_abits;  // [slot][n]
     uint8_t* v_status; int32_t* v_wait; uint16_t* v_rule;
     void* sort_tmp; size_t sort_tmp_bytes;
-    void* scan_tmp; size_t scan_tmp_bytes;
     // heavy / light split (sf_heavy.h)
     uint32_t seg_cap;                                   // min(max_batch, R)
     uint32_t* segflag; uint8_t* seg_mode;
-    uint32_t* light_list; uint32_t* heavy_list; uint32_t* counters;
+    uint32_t* light_list; uint32_t* heavy_list;
+    uint32_t* counters;                                 // [WC_COUNT] list lengths and cursors of the batch (WorkCounter)
     uint32_t* lcounts;                                  // [2][LCLS] light segments per length class: generic, lean QPS
     uint32_t loff[LCLS];                                // light_list region of each class: generic from the
-    uint32_t lcap[LCLS];                                //   front, lean QPS (SM_LIGHTQ) from the back                                // light_list region of each length class   // [0] n_light [1] n_heavy front [2] hw slots [3] sec slots [4] n_heavy back
-                                                                      // [5] n_stream front [6] n_stream back
-    int64_t* pcg; void* pscan_tmp; size_t pscan_tmp_bytes;
+    uint32_t lcap[LCLS];                                //   front, lean QPS (SM_LIGHTQ) from the back
+    int64_t* pcg;                                       // [n] inclusive prefix of entry acquireCount (k_segs_out)
     void* segs_lb;                                      // k_segs_red / k_segs_out tile totals (segs_lb_bytes)
     uint2* fill_tiles; uint32_t fill_tile_cap;         // [2][cap] (segment, tile) of each class for k_heavy_fill
     uint32_t* fill_ntiles;                              // [2] tiles per class
@@ -243,7 +261,7 @@ struct Work {
     uint32_t stream_grid;                               // persistent k_heavy_stream workgroups (2 per CU)
     uint64_t* hticks;                                   // [max heavy] k_heavy_decide clock per segment (timing)
     uint32_t* stream_list;                              // THREAD / RL heavy segments (k_heavy_stream)
-    uint32_t* xw_list;                                  // [N / XW_MIN + 1] xflow segments of the wave walk (counters[12])
+    uint32_t* xw_list;                                  // [N / XW_MIN + 1] xflow segments of the wave walk (counters[WC_XW_LIST])
     uint64_t* sticks;                                   // [max heavy] k_heavy_stream clock per segment (timing)
     unsigned long long* passbits;                       // [n/64+2] pass bit per sorted entry (heavy segments)
     uint32_t* exit_of;                                  // [n] sorted index of each entry's exit, ~0 if none
@@ -252,7 +270,7 @@ struct Work {
     uint32_t* tile_rc;                                  // [fill_tile_cap] runs starting in each stream tile -> run id base
     uint32_t* seg_rb; uint32_t* seg_re;                 // [seg_cap] run id range of each SM_THREAD segment
     // (THREAD run mode also borrows buffers dead after the sort: rid = keys_in,
-    //  run_start = head_scan, run_pre = keys_out, entry records = pv_in; sf_kernels.hip heavy_ctx)
+    //  run_start = head_scan, run_pre = keys_out, entry records = pv_in; sf_heavy.hip heavy_ctx)
     uint32_t* vs_cursor;                                // [VS_CURSORS(N)] fill counts of the verdict scatter's buckets
 // origin nodes (sf_origin.hip), batches with origins only
     uint32_t* s_origin;                                 // [N] origin id in sorted order
@@ -328,8 +346,9 @@ constexpr uint8_t SYSR_AUTH = 6;
 // -1 it passed (the exit is live, like an entry of an earlier batch), -2 blocked
 constexpr int64_t EREF_DEAD = -2;
 
-// ---- launchers (sf_kernels.hip) ----
-hipError_t query_temp_bytes(uint32_t max_n, size_t* sort_bytes, size_t* scan_bytes, size_t* pscan_bytes);
+// ---- launchers the host runtime calls (batch pipeline: sf_segs.hip, sf_decide.hip, sf_packed.hip,
+// sf_state.hip; what those files call among themselves: sf_launch.h) ----
+hipError_t query_temp_bytes(uint32_t max_n, size_t* sort_bytes);
 hipError_t launch_init_state(const DevState& st, hipStream_t s);
 hipError_t launch_rdesc(const DevState& st, hipStream_t s);   // RDesc of every resource from the rule tables
 hipError_t launch_entry_node(const DevState& st, const DevBatch& b, const uint8_t* vstatus, EntryNode* en,
@@ -373,7 +392,7 @@ struct OxPlan { uint32_t n_heavy, n_pairs; OxWin win; };   // the batch's origin
 hipError_t launch_decide(const DevState& st, Work& w, const DevBatch& b, const DevVerdicts& out,
                          hipStream_t s, hipStream_t s2, hipStream_t s3, hipStream_t s4, hipEvent_t* ev, bool timing,
                          const OxPlan* ox = nullptr, bool classify = false, hipStream_t sv = nullptr);
-// sf_packed_batch -> SoA (sf_kernels.hip); tile_cnt: [n / 4096 + 1] uint2.  ev4 / ms_end /
+// sf_packed_batch -> SoA (sf_packed.hip); tile_cnt: [n / 4096 + 1] uint2.  ev4 / ms_end /
 // n_ms: the narrow form (ev null)
 hipError_t launch_pk_expand(const uint64_t* ev, const uint32_t* ev4, const uint32_t* ms_end, uint32_t n_ms,
                             const int64_t* xref, const int64_t* xcts, const int32_t* cext,
@@ -403,10 +422,35 @@ hipError_t launch_ox_rehash(const ParamSlot* old_tab, uint64_t old_n, ParamSlot*
                             int32_t* err, hipStream_t s);
 hipError_t launch_aux_find(const DevState& st, uint64_t hi, uint64_t lo, uint32_t* out, hipStream_t s);
 constexpr size_t ACC_BYTES = 72;                         // sizeof(Acc)
-// pipeline events: 0 start, 1 segments, 2 classified, 3 joined, 4 scattered,
-// 5 fork, 6 join (stream B), 7 heavy decided, 8 heavy filled, 9 light decided, 10 before classify,
-// 11 stream start (stream C), 12 stream done (stream C), 13 stream fill + apply done (stream C),
-// 14 origin-node pass done (stream B)
-constexpr int SF_NUM_EVENTS = 18;
+// The events of one batch (Slot::evs), recorded by launch_sort, launch_classify
+// and launch_decide.  Streams: the sort stream (launch_sort's), and in the
+// decide phase A (launch_decide's s), B (s2), C (s3), 4 (s4: the wave walk) and
+// the side stream (sv: the verdict scatter of an asynchronous batch, else A).
+// "timing": recorded only when the engine times its kernels, read by acc_timing
+// alone; the fork / join events are recorded for every batch.
+enum PipeEvent : int {
+    EV_SORT_START = 0,     // sort stream, before the radix sort; timing
+    EV_SORTED,             // sort stream, radix sort done and segflag cleared, the segment table starts; timing
+    EV_CLASSIFIED,         // launch_classify's stream (the sort stream, or A), after k_fill_tiles; timing
+    EV_JOINED,             // A, after B, C and 4 have joined it; timing (end of decide_ms, start of scatter_ms)
+    EV_SCATTERED,          // the scatter's stream (side stream, or A), after the scatter and the origin-pass join; timing
+    EV_FORK,               // A, after the clearing fill and k_gather_exit: B, C and 4 wait on it; acc_timing reads it
+                           // as the start of the light and heavy-decide times
+    EV_JOIN_B,             // B, after its heavy kernels and the lean QPS walks: A waits on it
+    EV_HEAVY_DECIDED,      // B, after k_heavy_decide; timing
+    EV_HEAVY_FILLED,       // B, after class 0's k_heavy_fill; timing
+    EV_LIGHT_DONE,         // C, after the light lanes and k_decide_x: A waits on it (the join of C); acc_timing reads it
+    EV_CLASSIFY_START,     // launch_classify's stream, after the clearing fill and before k_classify; timing
+    EV_STREAM_START,       // A, before k_heavy_stream (after launch_thr_prep); nobody waits, acc_timing reads it
+    EV_STREAM_DONE,        // A, after k_heavy_stream; nobody waits, acc_timing reads it
+    EV_JOINED_BC,          // A, after its waits on EV_JOIN_B and EV_LIGHT_DONE and ahead of its wait on
+                           // EV_XWAVE_DONE: B waits on it before the origin pass, which so runs beside the wave walk
+    EV_ORIGIN_DONE,        // B, after the origin pass (launch_ox_apply): A and the side stream wait on it
+    EV_XWAVE_DONE,         // 4, after k_decide_xw: A waits on it
+    EV_LEAN_DONE,          // B, after the lean QPS walks (just before EV_JOIN_B); nobody waits, acc_timing reads it
+    EV_SCATTER_FORK,       // A, before the scatter when it goes to the side stream, which waits on it
+    SF_NUM_EVENTS          // 18
+};
+static_assert(SF_NUM_EVENTS == 18, "one enumerator per pipeline event");
 
 }  // namespace sf

@@ -3,7 +3,7 @@
 // values, the collections' element CSR -- expanded into the dense slot-major
 // arrays the sort and decide phases read (DevBatch nargs / atag / abits,
 // stride n), and the validation of every index before it is used.  One body
-// for the device kernels (k_pk_args_check / k_pk_args, sf_kernels.hip) and the host check
+// for the device kernels (k_pk_args_check / k_pk_args, sf_packed.hip) and the host check
 // (tests/packed_args_check.cpp): nothing here needs the HIP runtime.
 //
 // The dense arrays are zero-filled (nargs, atag) before the expansion, so an

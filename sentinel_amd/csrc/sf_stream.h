@@ -21,7 +21,7 @@
 //    a search over the chunk's LDS timestamps, then takes the first candidate
 //    of a 64-event ballot.  Work is proportional to passes plus chunks.
 #pragma once
-#include "sf_heavy.h"
+#include "sf_launch.h"
 
 namespace sf {
 
@@ -32,20 +32,6 @@ constexpr int HS_CH = HS_T * HS_PL;       // events per chunk (2048)
 constexpr int HS_LDS_WORDS = (2 * HS_CH * 8 + 2 * HS_CH * 4) / 8;   // RL: 48 KiB as u64 words
 constexpr uint32_t CODE_EXIT = 0x80000000u;
 constexpr uint32_t CODE_DEAD = 0x7fffffffu;   // exit distance field: entry not in this segment (never live)
-
-struct StreamCtx {
-    const uint32_t* list; const uint32_t* n_list;   // n_list[0] front count, n_list[1] back count
-    uint32_t seg_cap;
-    uint64_t* sticks;
-    uint32_t* next;                                 // work queue head (k_heavy_stream)
-};
-
-__device__ __forceinline__ bool stream_at(const StreamCtx& sc, uint32_t b, uint32_t* s) {
-    const uint32_t nf = sc.n_list[0], nb = sc.n_list[1];
-    if (b < nf) { *s = sc.list[b]; return true; }
-    if (b < nf + nb) { *s = sc.list[sc.seg_cap - 1 - (b - nf)]; return true; }
-    return false;
-}
 
 // Workgroup barrier for LDS hand-offs only: waits for this wave's LDS ops, not
 // for its outstanding global stores and atomics (the pass bits are read by
@@ -208,16 +194,7 @@ __device__ __forceinline__ bool thr_mark_exit(ThrLds& L, unsigned long long* lxf
 // entirely: one vector read of their ring words finds the next one.  Inside a
 // window, only events that change the thread count are visited; the exits of
 // the window's passed entries are marked in one vector step after it.
-// inclusive scans over the 64 lanes of a wavefront (DPP: row shifts, then row broadcasts)
-__device__ __forceinline__ int wave_scan_add(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);     // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);     // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);     // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);     // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);     // row_bcast:15
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);     // row_bcast:31
-    return v;
-}
+// inclusive max scan over the 64 lanes of a wavefront (wave_scan_add: sf_launch.h)
 __device__ __forceinline__ int wave_scan_max(int v) {
     constexpr int ID = INT32_MIN;
     v = max(v, __builtin_amdgcn_update_dpp(ID, v, 0x111, 0xf, 0xf, false));

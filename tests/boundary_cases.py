@@ -26,7 +26,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # ---- the engine's constants, restated (test_constants_match_the_source) ----
 RUN_RC = 8192               # sf_stream.h: run-mode live-exit counter ring (runs ahead)
 LX_WORDS = 2048             # sf_stream.h: window-walk live-exit ring (64-event words)
-SL_TILE = 4096              # sf_kernels.hip: k_segs_red / k_segs_out positions per tile
+SL_TILE = 4096              # sf_segs.hip: k_segs_red / k_segs_out positions per tile
 RS_TILE = 4096              # sf_rsort.h RsGeom::TILE: radix pass tile
 RS_CE = 16                  # sf_rsort.h: consecutive keys per thread of k_rs_count
 FILL_TILE = 2048            # sf_internal.h: k_heavy_fill tile
@@ -70,7 +70,7 @@ def source_constants():
         assert len(m) == 1, (pat, m)
         return m[0]
     stream, heavy, internal = text("sf_stream.h"), text("sf_heavy.h"), text("sf_internal.h")
-    kern, rsort, eng = text("sf_kernels.hip"), text("sf_rsort.h"), text("sf_engine.cpp")
+    kern, rsort, eng = text("sf_segs.hip"), text("sf_rsort.h"), text("sf_engine.cpp")
     out = {}
     out["RUN_RC"] = int(one(stream, r"constexpr uint32_t RUN_RC = (\d+);"))
     out["LX_WORDS"] = int(one(stream, r"constexpr uint32_t LX_WORDS = (\d+);"))

@@ -611,7 +611,7 @@ def source_lines():
     def text(name):
         with open(os.path.join(_CSRC, name)) as f:
             return f.read()
-    dec, internal, kern = text("sf_decide.h"), text("sf_internal.h"), text("sf_kernels.hip")
+    dec, internal, kern = text("sf_decide.h"), text("sf_internal.h"), text("sf_segs.hip")
 
     def one_(src, pat):
         m = re.findall(pat, src)

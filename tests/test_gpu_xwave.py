@@ -1,4 +1,4 @@
-"""The wave walk of long xflow segments (sf_kernels.hip k_decide_xw) against
+"""The wave walk of long xflow segments (sf_xwave.hip k_decide_xw) against
 the C oracle.
 
 A resource whose rules all check DIRECT (its ClusterNode, or an origin node
