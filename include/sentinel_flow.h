@@ -127,8 +127,10 @@ void sf_config_default(sf_config* cfg);
  *   CHAIN -> the resource's DefaultNode of context ref_resource (a context id)
  *       when the event's context is that one, else pass
  *   anything else -> no node -> pass.
- * cluster_mode: ClusterStateManager is not started in the engine's process
- * (pickClusterService() == null, FlowRuleChecker.java:163-203), so a cluster
+ * cluster_mode: a cluster rule that sf_load_cluster_binds binds to a flowId
+ * asks the engine's own token server (embedded mode, see there).  For every
+ * other cluster rule the engine behaves as if ClusterStateManager were not
+ * started (pickClusterService() == null, FlowRuleChecker.java:163-203): the
  * rule is checked locally when cluster_fallback (fallbackToLocalWhenFail,
  * ClusterFlowConfig default true) is set and passes otherwise.  Cluster
  * token rules themselves go to sf_load_cluster_rules (the token server).   */
@@ -432,6 +434,10 @@ typedef struct sf_stats {         /* device-clock timings, summed over sf_submit
      * events the serial part walked */
     uint64_t xw_chunks_exact, xw_chunks_serial, xw_rounds, xw_serial_events;
     uint64_t sys_exchanges;       /* all-gathers of sf_submit_node's per-window exchange (SF_SYSX_MSG_BYTES or SF_SYSX_WIDE_MSG_BYTES each, plan step) */
+    /* the wave route of bound cluster rules (k_decide_xcl, sf_load_cluster_binds):
+     * chunks the wavefront solved, chunks lane 0 replayed serially; since the
+     * binds were last loaded */
+    uint64_t xcl_chunks_wave, xcl_chunks_serial;
 } sf_stats;
 
 typedef struct sf_heavy_profile { /* diagnostics: one heavy segment of the last sf_submit */
@@ -626,6 +632,66 @@ int  sf_load_cluster_rules(sf_engine* e, const sf_cluster_flow_rule* flow, uint3
                            const sf_cluster_param_rule* param, uint32_t n_param,
                            const sf_hot_item* items, uint32_t n_items);
 int  sf_request_tokens(sf_engine* e, const sf_token_batch* in, sf_token_results* out);
+/* Embedded token server (DefaultEmbeddedTokenServer): cluster-mode flow rules
+ * take their tokens from this engine's token server inside sf_submit*.
+ *   rule_index  index into the array last given to sf_load_flow_rules
+ *   flow_id     rule.getClusterConfig().getFlowId()
+ * A bound rule is decided as if ClusterStateManager.isServer() were true and
+ * the engine's token server were EmbeddedClusterTokenServerProvider.getServer():
+ * when FlowRuleChecker.checkFlow reaches it, canPassCheck goes to
+ * passClusterCheck before any node is selected (FlowRuleChecker.java:75-77),
+ * so the request is made whatever the rule's limit_app, strategy or the
+ * event's origin.  The request is DefaultTokenService.requestToken(flow_id,
+ * acquireCount, prioritized) at the event's ts_ms, exactly what
+ * sf_request_tokens decides for a batch of that one request at that point of
+ * the serial order (BAD_REQUEST for a count <= 0, NO_RULE_EXISTS, the
+ * namespace's GlobalRequestLimiter, then ClusterFlowChecker.acquireClusterToken
+ * with every ClusterFlowEvent counter; the threshold is the
+ * sf_cluster_flow_rule's, not the local rule's).  applyTokenResult (:205-230):
+ *   OK           the rule passes, the next rule is checked
+ *   SHOULD_WAIT  sleep(waitInMs), then passes: wait_ms += waitInMs, the entry
+ *                is a normal pass (SF_V_PASS_WAIT), the clock does not advance
+ *   BLOCKED      SF_V_BLOCK_FLOW, rule_idx = the rule
+ *   NO_RULE_EXISTS, BAD_REQUEST, FAIL, TOO_MANY_REQUEST  fallbackToLocalOrPass:
+ *                what an unbound cluster rule does (local check with node
+ *                selection when cluster_fallback, else pass)
+ * An entry that never reaches the rule (SF_EV_BLOCKED, authority, a forced
+ * SystemRule block, a ParamFlow block, an earlier flow rule's block) makes no
+ * request; exits make none.
+ * n == 0 clears the table: nothing then differs from an engine that never had
+ * one.  A cluster rule without a bind keeps the behaviour described at
+ * sf_flow_rule.  sf_load_flow_rules clears the binds (rule indices change):
+ * load the flow rules first, then the binds.  A flow_id that
+ * sf_load_cluster_rules does not (or no longer) hold is legal: the server
+ * answers NO_RULE_EXISTS.
+ * Errors, decided before anything changes: SF_ERR_INVALID for a rule_index out
+ * of range, a rule with cluster_mode == 0 (or dropped as invalid by the load),
+ * flow_id <= 0 (FlowRuleUtil.validClusterRuleId), two binds naming one rule;
+ * SF_ERR_UNSUPPORTED when shard_count != 1 (a resource's shard and a flowId's
+ * owner are different maps, as for sf_request_rls).
+ * Order.  A resource with a bound rule is decided on the xflow walk, one lane
+ * per group in submission order.  A namespace with a GlobalRequestLimiter
+ * (max_allowed_qps >= 0) is one sequential gate (GlobalRequestLimiter.java:
+ * 46-55): all resources bound into it form ONE group, so a limiter serialises
+ * its namespace's bound traffic on one lane, exactly as the reference's lock
+ * does; leave the limiter off a namespace that carries hot bound resources.
+ * Resources bound to one flowId are joined too.  A long segment (256 events
+ * or more) of a resource that is alone in its group, whose only flow rule is
+ * the bound rule with strategy DIRECT, with no ParamFlow / gateway rule or breaker, a loaded flowId
+ * and no limiter on its namespace is decided by one wavefront instead
+ * (k_decide_xcl; sf_stats.xcl_chunks_wave / xcl_chunks_serial).  A device
+ * failure during any of the loads below leaves every cluster rule decided as
+ * unbound until a load succeeds.  Groups depend on the flow
+ * rules, binds, cluster rules and namespaces, and are rebuilt by whichever
+ * load comes last; with binds loaded each of those loads, and
+ * sf_request_tokens, sf_request_rls, sf_serve_frames and sf_cluster_sum, wait
+ * for asynchronous submit batches in flight first.  Time order across calls
+ * stays the caller's precondition.
+ * Out of scope: cluster-mode ParamFlowRules in the chain (sf_param_rule has no
+ * cluster fields), token-client mode, concurrency tokens from the chain,
+ * sharded engines.                                                          */
+typedef struct sf_cluster_bind { uint32_t rule_index; uint32_t pad; int64_t flow_id; } sf_cluster_bind;
+int  sf_load_cluster_binds(sf_engine* e, const sf_cluster_bind* binds, uint32_t n);
 /* Token server over the GPUs of a node: one engine per GPU,
  * each loaded with ALL cluster rules and namespaces, with shard_count /
  * shard_index of its sf_config; a request is decided by its owner shard only

@@ -1,5 +1,6 @@
 package com.alibaba.csp.sentinel.gpu;
 
+import com.alibaba.csp.sentinel.cluster.ClusterStateManager;
 import com.alibaba.csp.sentinel.property.PropertyListener;
 import com.alibaba.csp.sentinel.property.SentinelProperty;
 import com.alibaba.csp.sentinel.slots.block.RuleConstant;
@@ -192,6 +193,19 @@ public final class GpuEngine {
         ruleVersion.incrementAndGet();
     }
 
+    /** Embedded mode: bind the server's own cluster-mode rules at all, and the flowIds left unbound. */
+    private static final boolean EMBEDDED_BIND =
+            !"false".equalsIgnoreCase(System.getProperty("sentinel.gpu.embedded.bind", "true"));
+    private static final java.util.Set<Long> EMBEDDED_SKIP = new java.util.HashSet<>();
+    static {
+        for (String s : System.getProperty("sentinel.gpu.embedded.skip", "").split(",")) {
+            if (!s.trim().isEmpty()) EMBEDDED_SKIP.add(Long.parseLong(s.trim()));
+        }
+    }
+
+    /** sf_cluster_bind (sentinel_flow.h): size and field offsets. */
+    private static final long CLUSTER_BIND_BYTES = 16, CLUSTER_BIND_RULE_INDEX = 0, CLUSTER_BIND_FLOW_ID = 8;
+
     /** Runs on the flusher thread (the engine is single-threaded). */
     void loadRulesNow() throws Throwable {
         try (Arena a = Arena.ofConfined()) {
@@ -222,6 +236,27 @@ public final class GpuEngine {
             }
             check((int) LOAD_FLOW.invokeExact(handle, fr, flow.size()));
             flowRulesByResource = byRes;
+            // embedded token server (DefaultEmbeddedTokenServer): this process serves the tokens, so its own
+            // cluster-mode rules take theirs from the engine's token server (FlowRuleChecker.java:163-181).
+            // sf_load_flow_rules has cleared the binds; rule_index is the rule's place in `flow`.
+            // -Dsentinel.gpu.embedded.bind=false keeps every cluster rule unbound (local fallback or pass);
+            // -Dsentinel.gpu.embedded.skip=<flowId,flowId,...> leaves single rules unbound (a very hot one:
+            // a bound resource is one wavefront's work per batch).
+            if (ClusterStateManager.isServer() && EMBEDDED_BIND) {
+                // sf_cluster_bind: {u32 rule_index, u32 pad, i64 flow_id}, 16 bytes
+                MemorySegment binds = a.allocate(CLUSTER_BIND_BYTES * Math.max(1, flow.size()), 8);
+                int nb = 0, at = 0;
+                for (FlowRule r : flow) {
+                    int index = at++;
+                    if (!r.isClusterMode() || r.getClusterConfig() == null || r.getClusterConfig().getFlowId() == null
+                            || r.getClusterConfig().getFlowId() <= 0
+                            || EMBEDDED_SKIP.contains(r.getClusterConfig().getFlowId())) continue;
+                    MemorySegment s = binds.asSlice((long) nb++ * CLUSTER_BIND_BYTES, CLUSTER_BIND_BYTES);
+                    s.set(JAVA_INT, CLUSTER_BIND_RULE_INDEX, index);
+                    s.set(JAVA_LONG, CLUSTER_BIND_FLOW_ID, r.getClusterConfig().getFlowId());
+                }
+                check((int) LOAD_CLUSTER_BINDS.invokeExact(handle, binds, nb));
+            }
 
             // param rules + hot items
             List<ParamFlowRule> param = ParamFlowRuleManager.getRules();

@@ -83,6 +83,9 @@ final class SentinelFlowNative {
             FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT));
     static final MethodHandle REQUEST_TOKENS = fn("sf_request_tokens",
             FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
+    // embedded token server: which cluster-mode flow rules take their tokens inside sf_submit
+    static final MethodHandle LOAD_CLUSTER_BINDS = fn("sf_load_cluster_binds",
+            FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT));
 
     /** sf_config (sentinel_flow.h): 19 fields, natural alignment: 88 bytes. */
     static final StructLayout CONFIG = MemoryLayout.structLayout(

@@ -144,6 +144,12 @@ class sf_cluster_flow_rule(C.Structure):
     ]
 
 
+class sf_cluster_bind(C.Structure):
+    """sf_load_cluster_binds: flow rule ``rule_index`` (of the last load_flow_rules list) asks the
+    engine's own token server for tokens of ``flow_id``."""
+    _fields_ = [("rule_index", C.c_uint32), ("pad", C.c_uint32), ("flow_id", C.c_int64)]
+
+
 class sf_cluster_param_rule(C.Structure):
     _fields_ = [
         ("flow_id", C.c_int64), ("count", C.c_double), ("threshold_type", C.c_int32),
@@ -234,7 +240,8 @@ class sf_stats(C.Structure):
                 ("wire_ms", C.c_double), ("sys_rounds", C.c_uint64), ("aux_nodes", C.c_uint64),
                 ("aux_capacity", C.c_uint64), ("aux_index_grows", C.c_uint64), ("param_table_grows", C.c_uint64),
                 ("xw_chunks_exact", C.c_uint64), ("xw_chunks_serial", C.c_uint64), ("xw_rounds", C.c_uint64),
-                ("xw_serial_events", C.c_uint64), ("sys_exchanges", C.c_uint64)]
+                ("xw_serial_events", C.c_uint64), ("sys_exchanges", C.c_uint64),
+                ("xcl_chunks_wave", C.c_uint64), ("xcl_chunks_serial", C.c_uint64)]
 
 
 class sf_heavy_profile(C.Structure):

@@ -144,8 +144,9 @@ __global__ void __launch_bounds__(128, PF ? SF_LIGHT_MINB : SF_LIGHT_NOPF_MINB) 
 }
 
 // One lane per xflow group segment (sf_xflow.h): origin / context / RELATE
-// rules (the long segments k_decide_xw takes excepted).
-template <int MAXS>
+// rules (the long segments k_decide_xw takes excepted).  EMB: with an embedded
+// token server (st.emb), bound cluster rules take their tokens from it.
+template <int MAXS, bool EMB>
 __global__ void __launch_bounds__(64) k_decide_x(DevState st, SegIO io, const uint32_t* seg_start,
                                                  const uint32_t* seg_res, const uint8_t* seg_mode,
                                                  const uint32_t* n_seg) {
@@ -153,7 +154,9 @@ __global__ void __launch_bounds__(64) k_decide_x(DevState st, SegIO io, const ui
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= *n_seg || seg_mode[s] != SM_XFLOW) return;
     if (xw_take(st, seg_res[s], seg_start[s + 1] - seg_start[s])) return;
-    decide_xgroup<MAXS>(st, io, seg_start[s], seg_start[s + 1]);
+    if constexpr (EMB)
+        if (xcl_take(st, seg_res[s], seg_start[s + 1] - seg_start[s])) return;       // k_decide_xcl's
+    decide_xgroup<MAXS, EMB>(st, io, seg_start[s], seg_start[s + 1]);
 }
 
 // One lane per short segment routed to the lean QPS walk (SM_LIGHTQ), from
@@ -209,8 +212,12 @@ static void launch_gather_exit(const DevState& st, Work& w, const DevBatch& b, h
 
 static void launch_decide_x(const DevState& st, const SegIO& io, const Work& w, uint32_t max_seg, hipStream_t s) {
     for_sample_count(st, [&](auto S) {
-        hipLaunchKernelGGL(k_decide_x<decltype(S)::value>, dim3(blocks(max_seg, 64)), dim3(64), 0, s, st, io,
-                           w.seg_start, w.seg_res, w.seg_mode, w.n_seg);
+        if (st.emb)
+            hipLaunchKernelGGL((k_decide_x<decltype(S)::value, true>), dim3(blocks(max_seg, 64)), dim3(64), 0, s, st,
+                               io, w.seg_start, w.seg_res, w.seg_mode, w.n_seg);
+        else
+            hipLaunchKernelGGL((k_decide_x<decltype(S)::value, false>), dim3(blocks(max_seg, 64)), dim3(64), 0, s, st,
+                               io, w.seg_start, w.seg_res, w.seg_mode, w.n_seg);
     });
 }
 
@@ -274,6 +281,7 @@ hipError_t launch_decide(const DevState& st, Work& w, const DevBatch& b, const D
     if (xw_on) {
         hipStreamWaitEvent(s4, ev[EV_FORK], 0);
         launch_xw(st, io, w, n, s4);
+        if (st.emb) launch_xcl(st, io, w, n, s4);      // bound-rule segments (sf_xcluster.hip), after the wave walk
         hipEventRecord(ev[EV_XWAVE_DONE], s4);
     }
     launch_heavy_decide(st, io, hc, max_heavy, s2);

@@ -115,6 +115,7 @@ static int work_fill(sf_engine* e, Work& w, DevPool& m) {
     SF_TRY(m.alloc(&w.sticks, nz((N / (w.heavy_min + 1) + 2) * 8)));
     SF_TRY(m.alloc(&w.stream_list, nz(SC * 4)));
     SF_TRY(m.alloc(&w.xw_list, nz((N / XW_MIN + 1) * 4)));
+    SF_TRY(m.alloc(&w.xcl_list, nz((N / XW_MIN + 1) * 4)));
     SF_TRY(m.alloc(&w.passbits, nz((N / 64 + 2) * 8)));
     SF_TRY(m.alloc(&w.exit_of, nz(N * 4)));
     SF_TRY(m.alloc(&w.lxfar, nz((N / 64 + 2) * 8)));
@@ -182,6 +183,7 @@ static int create(sf_engine* e) {
         else HIP_TRY(hipStreamCreateWithFlags(&e->sstream, hipStreamNonBlocking));
     }
     if (const char* v = getenv("SF_SERIAL_STREAMS")) e->serial = v[0] == '1';
+    if (const char* v = getenv("SF_XCL_MIN")) e->xcl_min = std::max<uint32_t>(XW_MIN, (uint32_t)strtoul(v, nullptr, 10));
     if (const char* v = getenv("SF_RLS_WAVE")) if (v[0] == '0') e->rls.wave_min = UINT32_MAX;
     {   // the side stream of asynchronous batches: stream C, whose light lanes end
         // first (diagnostics SF_SIDE: 0 none -- on `stream` as before round 6 --,
@@ -568,6 +570,78 @@ static int prepare_origins(sf_engine* e, Slot& sl, const DevBatch& b, hipStream_
 }
 
 
+// The xflow groups (sf_xflow.h build_xmap / build_xw) and the embedded token
+// server's tables (sf_token.h EmbState) from the host copies of the four loads
+// they depend on: flow rules, binds, cluster rules, namespaces.  Whichever of
+// those loads comes last calls this, so the groups do not depend on the order
+// of the loads.  The caller holds e->mu and has drained.
+extern "C++" int xgroups_rebuild(sf_engine* e) {
+    const std::vector<DevRule>& dr = e->host_rules;
+    const std::vector<uint32_t>& off = e->host_rule_off;
+    if (off.empty()) return SF_OK;                                  // no flow rule load yet: nothing to group
+    const bool emb = !e->binds.empty();
+    std::vector<int64_t> bind;
+    std::vector<int32_t> bind_ns;
+    std::vector<uint8_t> bind_wave;              // the flowId is loaded and no limiter gates it (k_decide_xcl)
+    // until the tables below are complete no walk may follow the old ones: a failure leaves the
+    // engine without an embedded token server (unbound behaviour), never with stale pointers
+    e->st.emb = nullptr;
+    if (emb) {
+        SF_TRY(tok_ready(e));
+        bind.assign(std::max<size_t>(1, dr.size()), 0);
+        bind_ns.assign(bind.size(), -1);
+        bind_wave.assign(bind.size(), 0);
+        for (const sf_cluster_bind& b : e->binds) {
+            const int32_t pos = e->flow_csr_of[b.rule_index];
+            bind[pos] = b.flow_id;
+            // the first cluster flow rule of an id is the one looked up, the first namespace of an id
+            // the one it counts in (tok_rebuild)
+            for (const sf_cluster_flow_rule& f : e->tok.host_cflow) {
+                if (f.flow_id != b.flow_id) continue;
+                bind_wave[pos] = 1;
+                for (size_t i = 0; i < e->tok.host_ns.size(); i++) {
+                    if (e->tok.host_ns[i].namespace_id != f.namespace_id) continue;
+                    if (e->tok.host_ns[i].max_allowed_qps >= 0) { bind_ns[pos] = (int32_t)i; bind_wave[pos] = 0; }
+                    break;
+                }
+                break;
+            }
+        }
+    }
+    std::vector<uint32_t> xmap;
+    const bool xflow = build_xmap(dr.data(), off.data(), e->R, xmap, emb ? bind.data() : nullptr,
+                                  emb ? bind_ns.data() : nullptr);
+    if (xflow) {
+        SF_TRY(ensure_aux(e));
+        if (!e->xmap_buf) SF_TRY(e->pool.alloc(&e->xmap_buf, (size_t)e->R * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpyAsync(e->xmap_buf, xmap.data(), (size_t)e->R * sizeof(uint32_t), hipMemcpyHostToDevice,
+                               e->stream));
+        std::vector<uint8_t> xw;
+        build_xw(dr.data(), off.data(), e->R, xmap, xw, emb ? bind.data() : nullptr, emb ? bind_wave.data() : nullptr);
+        if (!e->xw_buf) SF_TRY(e->pool.alloc(&e->xw_buf, (size_t)e->R));
+        HIP_TRY(hipMemcpyAsync(e->xw_buf, xw.data(), (size_t)e->R, hipMemcpyHostToDevice, e->stream));
+    }
+    if (emb) {
+        e->pool.release(e->emb_bind);
+        SF_TRY(e->pool.alloc(&e->emb_bind, bind.size() * sizeof(int64_t)));
+        HIP_TRY(hipMemcpyAsync(e->emb_bind, bind.data(), bind.size() * sizeof(int64_t), hipMemcpyHostToDevice, e->stream));
+        if (!e->emb_dev) SF_TRY(e->pool.alloc(&e->emb_dev, sizeof(EmbState)));
+        if (!e->emb_stats) SF_TRY(e->pool.alloc(&e->emb_stats, 2 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(e->emb_stats, 0, 2 * sizeof(unsigned long long), e->stream));
+        const EmbState h{e->tok.ts, e->emb_bind, e->emb_stats, e->xcl_min, 0};
+        HIP_TRY(hipMemcpyAsync(e->emb_dev, &h, sizeof h, hipMemcpyHostToDevice, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->st.xmap = xflow ? e->xmap_buf : nullptr;
+    e->st.xw = xflow ? e->xw_buf : nullptr;
+    e->st.emb = emb ? e->emb_dev : nullptr;
+    // the wave walk's stream, created at the first table that routes to it and
+    // after the pipeline's four (a stream created earlier changes which hardware
+    // queue each of those gets: config 3 lost 2.3 ms/step to a shared queue)
+    if (e->st.xw && !e->stream4) HIP_TRY(hipStreamCreateWithFlags(&e->stream4, hipStreamNonBlocking));
+    return SF_OK;
+}
+
 int sf_load_flow_rules(sf_engine* e, const sf_flow_rule* rules, uint32_t n) {
     if (!e || (n && !rules)) return fail(SF_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(e->mu);
@@ -604,6 +678,10 @@ int sf_load_flow_rules(sf_engine* e, const sf_flow_rule* rules, uint32_t n) {
     std::vector<uint32_t> fill(off.begin(), off.end() - 1);
     std::vector<DevRule> dr(valid.size());
     std::vector<DevRuleState> ds(valid.size());
+    // every check has passed: from here the tables move.  The binds name positions of the old rule
+    // table, so they go first: a failure below leaves every cluster rule decided as unbound
+    e->st.emb = nullptr;
+    e->binds.clear();
     e->flow_pos.assign(valid.size(), 0);
     for (size_t k = 0; k < valid.size(); k++) {
         const sf_flow_rule& r = *valid[k];
@@ -612,19 +690,6 @@ int sf_load_flow_rules(sf_engine* e, const sf_flow_rule* rules, uint32_t n) {
         DevRule d = make_dev_rule(r, e->cfg.cold_factor, (int32_t)k, valid_ref[k]);
         dr[pos] = d;
         ds[pos] = fresh_rule_state();
-    }
-    std::vector<uint32_t> xmap;
-    const bool xflow = build_xmap(dr.data(), off.data(), e->R, xmap);
-    if (xflow) {
-        SF_TRY(ensure_aux(e));
-        if (!e->xmap_buf) SF_TRY(e->pool.alloc(&e->xmap_buf, (size_t)e->R * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpyAsync(e->xmap_buf, xmap.data(), (size_t)e->R * sizeof(uint32_t), hipMemcpyHostToDevice,
-                               e->stream));
-        std::vector<uint8_t> xw;
-        build_xw(dr.data(), off.data(), e->R, xmap, xw);
-        if (!e->xw_buf) SF_TRY(e->pool.alloc(&e->xw_buf, (size_t)e->R));
-        HIP_TRY(hipMemcpyAsync(e->xw_buf, xw.data(), (size_t)e->R, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
     }
     e->n_flow = (uint32_t)valid.size();
     {   // which segment classes the rules allow (launches of absent classes are skipped)
@@ -645,13 +710,13 @@ int sf_load_flow_rules(sf_engine* e, const sf_flow_rule* rules, uint32_t n) {
     HIP_TRY(hipMemcpyAsync((void*)e->st.rule_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(launch_rdesc(e->st, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    e->st.xmap = xflow ? e->xmap_buf : nullptr;
-    e->st.xw = xflow ? e->xw_buf : nullptr;
-    // the wave walk's stream, created at the first table that routes to it and
-    // after the pipeline's four (a stream created earlier changes which hardware
-    // queue each of those gets: config 3 lost 2.3 ms/step to a shared queue)
-    if (e->st.xw && !e->stream4) HIP_TRY(hipStreamCreateWithFlags(&e->stream4, hipStreamNonBlocking));
-    return SF_OK;
+    // the xflow groups; rule indices changed, so the binds of the embedded token server are gone
+    e->host_rules = std::move(dr); e->host_rule_off = std::move(off);      // (uploaded and synchronised above)
+    e->flow_csr_of.assign(n, -1); e->flow_cluster.assign(n, 0);
+    for (size_t k = 0; k < valid.size(); k++) e->flow_csr_of[(size_t)(valid[k] - rules)] = (int32_t)e->flow_pos[k];
+    for (uint32_t i = 0; i < n; i++) e->flow_cluster[i] = rules[i].cluster_mode != 0;
+    e->binds.clear();
+    return xgroups_rebuild(e);
 }
 
 // ParamFlowRule.equals of two loaded rules of one resource (their item lists as loaded)
@@ -2120,6 +2185,12 @@ int sf_get_stats(sf_engine* e, sf_stats* out) {
         unsigned long long x[4];
         HIP_TRY(hipMemcpy(x, e->st.xw_stats, sizeof x, hipMemcpyDeviceToHost));
         out->xw_chunks_exact = x[0]; out->xw_chunks_serial = x[1]; out->xw_rounds = x[2]; out->xw_serial_events = x[3];
+    }
+    if (e->emb_stats) {
+        unsigned long long x[2];
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipMemcpy(x, e->emb_stats, sizeof x, hipMemcpyDeviceToHost));
+        out->xcl_chunks_wave = x[0]; out->xcl_chunks_serial = x[1];
     }
     return SF_OK;
 }

@@ -272,6 +272,18 @@ struct sf_engine {
     EntryNode* en = nullptr;
     EntryAcc* en_acc = nullptr;
     ncclComm_t comm = nullptr;
+    // embedded token server (sf_load_cluster_binds; xgroups_rebuild): host copies of the flow rule
+    // tables the groups are rebuilt from, the raw rule array's CSR positions (-1: dropped as invalid)
+    // and cluster_mode flags, the binds, and the device tables DevState::emb points to
+    std::vector<DevRule> host_rules;
+    std::vector<uint32_t> host_rule_off;
+    std::vector<int32_t> flow_csr_of;
+    std::vector<uint8_t> flow_cluster;
+    std::vector<sf_cluster_bind> binds;
+    EmbState* emb_dev = nullptr;
+    int64_t* emb_bind = nullptr;
+    unsigned long long* emb_stats = nullptr;      // [2] EmbState::stats
+    uint32_t xcl_min = XCL_MIN;                   // diagnostics (SF_XCL_MIN=<n>): k_decide_xcl's shortest segment
     // xflow walk (sf_xflow.h): group keys and the origin / context node pool
     uint32_t* xmap_buf = nullptr;
     uint8_t* xw_buf = nullptr;
@@ -288,6 +300,11 @@ struct sf_engine {
 // ---- helpers of sf_engine.cpp that the other files call (the caller holds e->mu)
 // Drain asynchronously submitted batches and report the first error of any of them
 int drain(sf_engine* e, bool all = false);
+// the xflow groups and the embedded token server's tables from the host copies of the flow rules,
+// binds, cluster rules and namespaces (drained)
+int xgroups_rebuild(sf_engine* e);
+// token state present (rules built, namespace limiter allocated)
+int tok_ready(sf_engine* e);
 // order `stream` after the last asynchronous ENTRY_NODE update
 int en_fence(sf_engine* e);
 // resource id -> local row of this shard (0: not this shard's)

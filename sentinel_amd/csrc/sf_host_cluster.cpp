@@ -139,6 +139,8 @@ int sf_load_namespaces(sf_engine* e, const sf_namespace* ns, uint32_t n) {
     if (!e || (n && !ns)) return fail(SF_ERR_INVALID, "null argument");
     if (n > 255) return fail(SF_ERR_UNSUPPORTED, "at most 255 namespaces");
     std::lock_guard<std::mutex> lk(e->mu);
+    const bool emb = !e->binds.empty();          // the chain asks this token server: batches in flight read its state
+    if (emb) { SF_TRY(drain(e)); e->st.emb = nullptr; }      // (the tables move: set again by xgroups_rebuild)
     e->tok.host_ns.assign(ns, ns + n);
     // GlobalRequestLimiter state of the loaded namespaces starts empty
     LimState z;
@@ -147,7 +149,8 @@ int sf_load_namespaces(sf_engine* e, const sf_namespace* ns, uint32_t n) {
     e->pool.release(e->tok.ts.lim);
     SF_TRY(e->pool.alloc(&e->tok.ts.lim, lim.size() * sizeof(LimState)));
     HIP_TRY(hipMemcpyAsync(e->tok.ts.lim, lim.data(), lim.size() * sizeof(LimState), hipMemcpyHostToDevice, e->stream));
-    return tok_rebuild(e, false);
+    SF_TRY(tok_rebuild(e, false));
+    return emb ? xgroups_rebuild(e) : SF_OK;     // a limiter joins the resources bound into its namespace
 }
 
 int sf_load_cluster_rules(sf_engine* e, const sf_cluster_flow_rule* flow, uint32_t n_flow,
@@ -166,6 +169,8 @@ int sf_load_cluster_rules(sf_engine* e, const sf_cluster_flow_rule* flow, uint32
         if ((uint64_t)param[i].item_offset + param[i].item_count > n_items) return fail(SF_ERR_INVALID, "hot item range");
     }
     std::lock_guard<std::mutex> lk(e->mu);
+    const bool emb = !e->binds.empty();
+    if (emb) { SF_TRY(drain(e)); e->st.emb = nullptr; }
     // nowCalls of a flowId that stays loaded is kept (ClusterFlowRuleManager.java:271-375)
     std::unordered_map<int64_t, int32_t> kept;
     if (e->cc.cs.now && !e->tok.host_cflow.empty()) {
@@ -179,6 +184,7 @@ int sf_load_cluster_rules(sf_engine* e, const sf_cluster_flow_rule* flow, uint32
     e->tok.host_cparam.assign(param, param + n_param);
     e->tok.host_citems.assign(items, items + n_items);
     int rc = tok_rebuild(e, true);
+    if (!rc && emb) rc = xgroups_rebuild(e);     // a bound flowId's namespace may have changed
     if (rc || !e->cc.cs.now) return rc;
     std::vector<int32_t> now(std::max<uint32_t>(n_flow, 1), 0);
     for (uint32_t i = 0; i < n_flow; i++) {                    // (the first rule of an id is the one looked up)
@@ -188,12 +194,42 @@ int sf_load_cluster_rules(sf_engine* e, const sf_cluster_flow_rule* flow, uint32
     return cc_tables(e, &now);
 }
 
+// Embedded token server (DefaultEmbeddedTokenServer): which cluster-mode flow
+// rules of sf_load_flow_rules ask this engine's token server from inside the
+// slot chain (FlowRuleChecker.passClusterCheck, FlowRuleChecker.java:163-203).
+// Every error is decided before anything changes.
+int sf_load_cluster_binds(sf_engine* e, const sf_cluster_bind* binds, uint32_t n) {
+    if (!e || (n && !binds)) return fail(SF_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    // a resource's shard and a flowId's owner are different maps (sf_token_shard)
+    if (n && e->cfg.shard_count != 1)
+        return fail(SF_ERR_UNSUPPORTED, "sf_load_cluster_binds on a sharded engine");
+    std::vector<uint8_t> seen(e->flow_csr_of.size(), 0);
+    for (uint32_t i = 0; i < n; i++) {
+        const sf_cluster_bind& b = binds[i];
+        if (b.rule_index >= e->flow_csr_of.size()) return fail(SF_ERR_INVALID, "cluster bind: rule_index out of range");
+        if (!e->flow_cluster[b.rule_index]) return fail(SF_ERR_INVALID, "cluster bind: the rule is not cluster_mode");
+        if (e->flow_csr_of[b.rule_index] < 0) return fail(SF_ERR_INVALID, "cluster bind: the rule was dropped as invalid");
+        if (b.flow_id <= 0) return fail(SF_ERR_INVALID, "cluster bind: flow_id must be > 0 (FlowRuleUtil.validClusterRuleId)");
+        if (seen[b.rule_index]++) return fail(SF_ERR_INVALID, "cluster bind: two binds name one rule");
+    }
+    SF_TRY(drain(e));   // pending batches were sorted under the old groups
+    const std::vector<sf_cluster_bind> old = e->binds;
+    e->binds.assign(binds, binds + n);
+    const int rc = xgroups_rebuild(e);
+    if (rc) {                                    // a device failure: back to the old binds if they can be rebuilt,
+        e->binds = old;                          // else (st.emb null) every cluster rule is decided as unbound
+        if (xgroups_rebuild(e)) e->binds.clear();
+    }
+    return rc;
+}
+
 // the scratch sizes of the work sets (sf_worksets.h) as rocPRIM states them
 static int tok_temp_query(uint32_t n, size_t* s8, size_t* s64, size_t* scan) { HIP_TRY(tok_query_temp(n, s8, s64, scan)); return SF_OK; }
 static int cc_temp_query(uint32_t n, size_t* bytes) { HIP_TRY(cc_query_temp(n, bytes)); return SF_OK; }
 
 // token state present (rules built, namespace limiter allocated); caller holds e->mu
-static int tok_ready(sf_engine* e) {
+extern "C++" int tok_ready(sf_engine* e) {
     if (!e->tok.ts.rules) SF_TRY(tok_rebuild(e, true));
     if (!e->tok.ts.lim) {
         LimState z; for (int k = 0; k < LIM_S; k++) { z.ws[k] = WS_NONE; z.v[k] = 0; }
@@ -209,6 +245,7 @@ int sf_request_tokens(sf_engine* e, const sf_token_batch* in, sf_token_results* 
     if (!in->flow_id || !in->count || !in->flags || !in->ts_ms) return fail(SF_ERR_INVALID, "missing request array");
     if ((in->param_tag == nullptr) != (in->param_bits == nullptr)) return fail(SF_ERR_INVALID, "param_tag/param_bits");
     std::lock_guard<std::mutex> lk(e->mu);
+    if (!e->binds.empty()) SF_TRY(drain(e));     // embedded mode: submit batches in flight take tokens too
     const uint32_t n = in->n;
     SF_TRY(tok_work_ensure(e->tok.tw, n, e->cfg.max_batch, tok_temp_query));
     SF_TRY(tok_ready(e));
@@ -293,6 +330,7 @@ int sf_serve_frames(sf_engine* e, const sf_wire_batch* in, sf_wire_out* out) {
     if (soff[S] >= (1ull << 31)) return fail(SF_ERR_CAPACITY, "wire batch must be < 2^31 bytes");
     if (soff[S] && !in->bytes) return fail(SF_ERR_INVALID, "null bytes");
     std::lock_guard<std::mutex> lk(e->mu);
+    if (!e->binds.empty()) SF_TRY(drain(e));
     out->n_frames = out->n_requests = out->n_responses = 0;
     const uint32_t n = (uint32_t)soff[S];
     if (soff[0] == n) {                          // nothing to read: every stream handled, no response
@@ -394,6 +432,7 @@ int sf_cluster_sum(sf_engine* e, int64_t flow_id, int event, int64_t now_ms, int
     if (!e || !out) return fail(SF_ERR_INVALID, "null argument");
     if (event < 0 || event >= CE_COUNT) return fail(SF_ERR_INVALID, "event");
     std::lock_guard<std::mutex> lk(e->mu);
+    if (!e->binds.empty()) SF_TRY(drain(e));
     *out = 0;
     for (size_t i = 0; i < e->tok.host_cflow.size(); i++) {
         if (e->tok.host_cflow[i].flow_id != flow_id) continue;
@@ -431,6 +470,7 @@ int sf_request_rls(sf_engine* e, const sf_rls_batch* in, sf_rls_results* out) {
     const bool host_in = in->mem == SF_MEM_HOST, host_out = out->mem == SF_MEM_HOST;
     if (n > e->cfg.max_batch) return fail(SF_ERR_CAPACITY, "more requests than max_batch");
     std::lock_guard<std::mutex> lk(e->mu);
+    if (!e->binds.empty()) SF_TRY(drain(e));
     RlsBatch b{};
     b.n = n; b.n_str = strings ? in->n_str : 0;
     // the lengths of the tables are their last offsets: read in place, or gathered on the device for one copy

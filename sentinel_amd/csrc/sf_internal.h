@@ -141,6 +141,11 @@ struct DevState {
     ParamSlot* xtab; uint64_t xcap_mask;
     const struct AuxChunk* ax_chunks;
     uint32_t* ax_count; uint32_t ax_cap;
+    // embedded token server (sf_token.h EmbState, sf_load_cluster_binds): the
+    // tables through which the xflow walk asks the engine's own token server
+    // for a bound cluster rule.  Null: no bind loaded, every cluster rule is
+    // decided as without a token service.
+    const struct EmbState* emb;
 };
 // one chunk of the origin / context node pool
 struct AuxChunk { Bucket* sec; Borrow* bor; Bucket* min; int64_t* thr; };
@@ -222,6 +227,7 @@ enum WorkCounter : uint32_t {
     WC_SHORT = 8,          // short generic light segments (front of class 0's light_list region)
     WC_SHORT_QPS = 9,      // short lean QPS light segments (its back; directly after WC_SHORT: k_classify, n_short)
     WC_XW_LIST = 12,       // xw_list entries (the wave walk's segments)
+    WC_XCL_LIST = 13,      // xcl_list entries (k_decide_xcl's segments)
     WC_COUNT = 16
 };
 static_assert(WC_STREAM_BACK == WC_STREAM_FRONT + 1 && WC_SHORT_QPS == WC_SHORT + 1, "adjacent counter pairs");
@@ -262,6 +268,7 @@ struct Work {
     uint64_t* hticks;                                   // [max heavy] k_heavy_decide clock per segment (timing)
     uint32_t* stream_list;                              // THREAD / RL heavy segments (k_heavy_stream)
     uint32_t* xw_list;                                  // [N / XW_MIN + 1] xflow segments of the wave walk (counters[WC_XW_LIST])
+    uint32_t* xcl_list;                                 // [N / XW_MIN + 1] bound-rule segments of k_decide_xcl (counters[WC_XCL_LIST])
     uint64_t* sticks;                                   // [max heavy] k_heavy_stream clock per segment (timing)
     unsigned long long* passbits;                       // [n/64+2] pass bit per sorted entry (heavy segments)
     uint32_t* exit_of;                                  // [n] sorted index of each entry's exit, ~0 if none

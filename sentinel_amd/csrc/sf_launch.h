@@ -105,6 +105,8 @@ void launch_heavy_apply(const DevState& st, const HeavyCtx& hc, const StreamCtx&
                         int cls, hipStream_t s);
 // sf_xwave.hip: k_decide_xw over Work::xw_list
 void launch_xw(const DevState& st, const SegIO& io, const Work& w, uint32_t n, hipStream_t s);
+// sf_xcluster.hip: k_decide_xcl over Work::xcl_list (engines with an embedded token server)
+void launch_xcl(const DevState& st, const SegIO& io, const Work& w, uint32_t n, hipStream_t s);
 // sf_scatter.hip: statuses of a decided batch, sorted order -> the caller's array (submission order)
 void launch_scatter(Work& w, uint32_t n, uint8_t* o_status, hipStream_t s);
 

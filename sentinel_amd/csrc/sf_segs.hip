@@ -266,6 +266,11 @@ __global__ void k_classify(DevState st, Work w, SortedEv ev) {
         const uint32_t p = wave_append(&w.counters[WC_XW_LIST], xw);
         if (xw) w.xw_list[p] = s;
     }
+    if (st.emb) {   // long segments of a resource whose only rule is a bound cluster rule (k_decide_xcl)
+        const bool xc = xs && xcl_take(st, res, hi - lo);
+        const uint32_t p = wave_append(&w.counters[WC_XCL_LIST], xc);
+        if (xc) w.xcl_list[p] = s;
+    }
     bool light = valid && !xs && hi - lo <= w.heavy_min;
     // a ParamFlow-only segment of more than 32 events is faster on the
     // wavefront-by-value path (SM_PARAM) than as one lane's serial table walk

@@ -70,10 +70,9 @@ struct TokState {
     uint32_t shard_count, shard_index;
 };
 
-#if defined(__HIPCC__)
 // flowId -> rule index of the flow (or param) rule table, -1: none (shared with sf_concur.hip)
-__device__ __forceinline__ uint64_t id_hash(int64_t id) { return mix64((uint64_t)id * 0x9e3779b97f4a7c15ULL); }
-__device__ __forceinline__ int32_t id_lookup(const TokState& ts, int64_t id, bool param) {
+SF_HD uint64_t id_hash(int64_t id) { return mix64((uint64_t)id * 0x9e3779b97f4a7c15ULL); }
+SF_HD int32_t id_lookup(const TokState& ts, int64_t id, bool param) {
     uint64_t i = id_hash(id) & ts.id_mask;
     for (uint64_t p = 0; p <= ts.id_mask; p++) {
         const IdSlot& s = ts.idtab[i];
@@ -84,13 +83,14 @@ __device__ __forceinline__ int32_t id_lookup(const TokState& ts, int64_t id, boo
     return -1;
 }
 
-// ---------------------------------------------------------------- ClusterMetric (one flowId, in LDS)
+// ---------------------------------------------------------------- ClusterMetric (one flowId; in LDS
+// for k_tok_decide, in HBM for the embedded requests of the slot chain; host-compilable for tests/)
 struct ClMetric {
     ClFlowState* s;
     int S, wl, I;
     double isec;
     // LeapArray.currentWindow(t) with ClusterMetricLeapArray.resetWindowTo (:45-71); -1: throwaway
-    __device__ int cur(int64_t t) {
+    SF_HD int cur(int64_t t) {
         const int idx = (int)((t / wl) % S);
         const int64_t ws = t - t % wl;
         ClBucket& b = s->b[idx];
@@ -113,7 +113,7 @@ struct ClMetric {
         }
         return -1;
     }
-    __device__ int64_t sum(int ev, int64_t t) {                  // ClusterMetric.getSum :47-55
+    SF_HD int64_t sum(int ev, int64_t t) {                  // ClusterMetric.getSum :47-55
         cur(t);
         int64_t r = 0;
         for (int k = 0; k < S; k++) {
@@ -122,19 +122,114 @@ struct ClMetric {
         }
         return r;
     }
-    __device__ double avg(int ev, int64_t t) { return (double)sum(ev, t) / isec; }
-    __device__ void add(int ev, int64_t n, int64_t t) {
+    SF_HD double avg(int ev, int64_t t) { return (double)sum(ev, t) / isec; }
+    SF_HD void add(int ev, int64_t n, int64_t t) {
         const int k = cur(t);
         if (k >= 0) s->b[k].c[ev] = wadd(s->b[k].c[ev], n);
     }
-    __device__ int64_t head_pass(int64_t t) {                    // getFirstCountOfWindow -> getValidHead
+    SF_HD int64_t head_pass(int64_t t) {                    // getFirstCountOfWindow -> getValidHead
         const int idx = (int)(((t + wl) / wl) % S);
         const ClBucket& b = s->b[idx];
         if (b.ws == WS_NONE || wsub(t, b.ws) > I) return 0;
         return b.c[CE_PASS];
     }
 };
+
+// ClusterFlowChecker.acquireClusterToken (:55-112) for one request that passed the namespace gate
+SF_HD void flow_decide(ClMetric& m, const ClRule& r, const TokState& ts, int32_t connected, int64_t t, int32_t c,
+                       bool prio, int8_t* st, int32_t* rem, int32_t* wt) {
+    const double latest = m.avg(CE_PASS, t);
+    const double thr = (r.threshold_type == SF_THRESHOLD_GLOBAL ? r.count : r.count * connected) * ts.exceed_count;
+    const double next = thr - latest - c;
+    if (next >= 0) {
+        m.add(CE_PASS, c, t); m.add(CE_PASS_REQUEST, 1, t);
+        if (prio) m.add(CE_OCCUPIED_PASS, c, t);
+        *st = SF_TOKEN_OK; *rem = j_d2i(next); *wt = 0;
+        return;
+    }
+    if (prio) {
+        const double occ_avg = m.avg(CE_WAITING, t);
+        if (occ_avg <= ts.max_occupy_ratio * thr) {
+            // ClusterMetric.tryOccupyNext :69-79, canOccupy :81-86
+            const double latest2 = m.avg(CE_PASS, t);
+            const int64_t head = m.head_pass(t);
+            const int64_t occupied = m.s->occ_pass;
+            if (latest2 + (double)((int64_t)c + occupied) - (double)head <= thr) {
+                m.s->occ_pass = wadd(m.s->occ_pass, c);          // addOccupyPass :74-78
+                m.s->occ_req = wadd(m.s->occ_req, 1);
+                m.s->has_occ = 1;
+                m.add(CE_WAITING, c, t);
+                const int32_t w = 1000 / m.S;
+                if (w > 0) { *st = SF_TOKEN_SHOULD_WAIT; *rem = 0; *wt = w; return; }
+            }
+        }
+    }
+    m.add(CE_BLOCK, c, t); m.add(CE_BLOCK_REQUEST, 1, t);
+    if (prio) m.add(CE_OCCUPIED_BLOCK, c, t);
+    *st = SF_TOKEN_BLOCKED; *rem = 0; *wt = 0;
+}
+
+// GlobalRequestLimiter.tryPass of one request at time t (RequestLimiter.java:51-87:
+// canPass is getQps() + 1 <= qpsAllowed, then add(1)); what k_ns_limit decides
+// for a window of requests, one request at a time
+SF_HD bool lim_try_pass(LimState& L, double qps, int64_t t) {
+    const int cur = (int)((t / LIM_WL) % LIM_S);
+    const int64_t ws = t - t % LIM_WL;
+    if (L.ws[cur] != ws) { L.ws[cur] = ws; L.v[cur] = 0; }
+    int64_t sum = 0;
+    for (int k = 0; k < LIM_S; k++)
+        if (k == cur || (L.ws[k] != WS_NONE && !(t - L.ws[k] > LIM_INTERVAL))) sum = wadd(sum, L.v[k]);
+    if (!((double)sum / 1.0 + 1 <= qps)) return false;
+    L.v[cur] = wadd(L.v[cur], 1);
+    return true;
+}
+
+// ---------------------------------------------------------------- embedded token server
+// The tables a slot-chain walk needs to ask the engine's own token server
+// (DefaultEmbeddedTokenServer: FlowRuleChecker.passClusterCheck calls
+// DefaultTokenService.requestToken in-process, FlowRuleChecker.java:163-203).
+// Lives in HBM; DevState::emb points to it (null: no bind loaded).
+struct EmbState {
+    TokState ts;                 // the token server's state, as sf_request_tokens uses it
+    const int64_t* bind;         // [flow rules, CSR position] flowId of a bound cluster rule, 0: not bound
+    unsigned long long* stats;   // [2] k_decide_xcl: chunks the wavefront solved, chunks lane 0 replayed
+    uint32_t xcl_min, pad;       // shortest segment k_decide_xcl takes (XCL_MIN; diagnostics: SF_XCL_MIN)
+};
+
+// DefaultTokenService.requestToken(flow_id, c, prio) at time t
+// (DefaultTokenService.java:39-64): what sf_request_tokens decides for a batch
+// of this one request -- notValidRequest, the rule lookup, the namespace's
+// GlobalRequestLimiter, then ClusterFlowChecker.acquireClusterToken on the
+// flowId's ClusterMetric in HBM.  One lane at a time per flowId and per limiter
+// namespace (the xflow groups, build_xmap).
+// Not inlined on the device: the walks that call it (k_decide_x) are at their
+// register limit already, and a rule without a bind never gets here.
+#if defined(__HIPCC__)
+__host__ __device__ __attribute__((noinline)) inline
+#else
+inline
 #endif
+void emb_request(const TokState& ts, int64_t flow_id, int64_t t, int32_t c, bool prio, int8_t* st, int32_t* wt) {
+    *wt = 0;
+    if (flow_id <= 0 || c <= 0) { *st = SF_TOKEN_BAD_REQUEST; return; }            // notValidRequest :66-68
+    const int32_t r = id_lookup(ts, flow_id, false);
+    if (r < 0) { *st = SF_TOKEN_NO_RULE_EXISTS; return; }                           // :45-47
+    const ClRule rule = ts.rules[r];
+    int32_t connected = 0;
+    if (rule.ns >= 0) {
+        const ClNs ns = ts.ns[rule.ns];
+        connected = ns.connected;
+        if (ns.has_limiter) {                                                       // ClusterFlowChecker.java:57-60
+            LimState L = ts.lim[rule.ns];
+            const bool ok = lim_try_pass(L, ns.max_qps, t);
+            ts.lim[rule.ns] = L;
+            if (!ok) { *st = SF_TOKEN_TOO_MANY_REQUEST; return; }
+        }
+    }
+    ClMetric m{&ts.fstate[r], rule.S, rule.wl, rule.interval, rule.interval / 1000.0};
+    int32_t rem;
+    flow_decide(m, rule, ts, connected, t, c, prio, st, &rem, wt);
+}
 
 struct TokBatch {
     uint32_t n;

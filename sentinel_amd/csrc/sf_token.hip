@@ -222,40 +222,6 @@ __global__ void k_tok_segments(const uint64_t* key, const uint32_t* head, const 
     if (last_valid) { const uint32_t ns = pos[j] + head[j]; *n_seg = ns; seg_start[ns] = j + 1; }
 }
 
-// ClusterFlowChecker.acquireClusterToken (:55-112) for one request that passed the namespace gate
-__device__ void flow_decide(ClMetric& m, const ClRule& r, const TokState& ts, int32_t connected, int64_t t, int32_t c,
-                            bool prio, int8_t* st, int32_t* rem, int32_t* wt) {
-    const double latest = m.avg(CE_PASS, t);
-    const double thr = (r.threshold_type == SF_THRESHOLD_GLOBAL ? r.count : r.count * connected) * ts.exceed_count;
-    const double next = thr - latest - c;
-    if (next >= 0) {
-        m.add(CE_PASS, c, t); m.add(CE_PASS_REQUEST, 1, t);
-        if (prio) m.add(CE_OCCUPIED_PASS, c, t);
-        *st = SF_TOKEN_OK; *rem = j_d2i(next); *wt = 0;
-        return;
-    }
-    if (prio) {
-        const double occ_avg = m.avg(CE_WAITING, t);
-        if (occ_avg <= ts.max_occupy_ratio * thr) {
-            // ClusterMetric.tryOccupyNext :69-79, canOccupy :81-86
-            const double latest2 = m.avg(CE_PASS, t);
-            const int64_t head = m.head_pass(t);
-            const int64_t occupied = m.s->occ_pass;
-            if (latest2 + (double)((int64_t)c + occupied) - (double)head <= thr) {
-                m.s->occ_pass = wadd(m.s->occ_pass, c);          // addOccupyPass :74-78
-                m.s->occ_req = wadd(m.s->occ_req, 1);
-                m.s->has_occ = 1;
-                m.add(CE_WAITING, c, t);
-                const int32_t w = 1000 / m.S;
-                if (w > 0) { *st = SF_TOKEN_SHOULD_WAIT; *rem = 0; *wt = w; return; }
-            }
-        }
-    }
-    m.add(CE_BLOCK, c, t); m.add(CE_BLOCK_REQUEST, 1, t);
-    if (prio) m.add(CE_OCCUPIED_BLOCK, c, t);
-    *st = SF_TOKEN_BLOCKED; *rem = 0; *wt = 0;
-}
-
 // one value's column of ClusterParameterLeapArray: getSum(value) at t (:52-66)
 // and addValue(value, c) (:72-84) -- only the value's own adds are counted
 __device__ __forceinline__ int64_t cp_sum(const CpSlot& s, int S, int wl, int I, int64_t t) {

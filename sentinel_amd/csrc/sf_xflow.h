@@ -26,9 +26,11 @@
 // for every entry with an origin): those are written after the verdicts by
 // the origin-node pass (sf_origin.hip).
 #pragma once
+#include <unordered_map>
 #include <vector>
 
 #include "sf_decide.h"
+#include "sf_token.h"
 
 namespace sf {
 
@@ -127,7 +129,9 @@ SF_HD int xflow_select(const DevState& st, const DevRule& r, uint32_t r0, uint32
 // -> ParamFlowSlot -> FlowSlot with per-rule node selection -> DegradeSlot,
 // then StatisticSlot's accounting.  cn / on / dn hold the nodes cl / oi / di
 // (XNONE: none held); a switch stores the held node back first.
-template <int MAXS>
+// EMB: the walk of an engine with an embedded token server (st.emb set): bound
+// cluster rules ask it.  The walks without it are compiled without that code.
+template <int MAXS, bool EMB = false>
 SF_HD void xg_event(const DevState& st, const SegIO& io, const ParamTable& pt, uint32_t lo, uint32_t j,
                     NodeWin<MAXS>& cn, NodeWin<MAXS>& on, NodeWin<MAXS>& dn, uint32_t& cl, uint32_t& oi,
                     uint32_t& di) {
@@ -240,6 +244,21 @@ SF_HD void xg_event(const DevState& st, const SegIO& io, const ParamTable& pt, u
             const bool prio = (fl & SF_EV_PRIO) != 0;
             for (uint32_t k = 0; k < r1 - r0; k++) {
                 const DevRule& r = st.rules[r0 + k];
+                // A bound cluster rule (sf_load_cluster_binds): canPassCheck goes to
+                // passClusterCheck before any node is selected (FlowRuleChecker.java:75-77),
+                // which asks the embedded token server (:163-181); applyTokenResult :205-230
+                int64_t fid = 0;
+                if constexpr (EMB) fid = st.emb->bind[r0 + k];
+                if (fid != 0) {
+                    int8_t ts; int32_t tw;
+                    emb_request(st.emb->ts, fid, now, c, prio, &ts, &tw);
+                    if (ts == SF_TOKEN_OK) continue;                                   // :207-209
+                    if (ts == SF_TOKEN_SHOULD_WAIT) { wait += tw; continue; }          // sleep(waitInMs), pass :210-218
+                    if (ts == SF_TOKEN_BLOCKED) {                                      // :225-227
+                        blocked = true; status = SF_V_BLOCK_FLOW; rule_idx = (int)k; break;
+                    }
+                    // NO_RULE_EXISTS, BAD_REQUEST, FAIL, TOO_MANY_REQUEST: fallbackToLocalOrPass :219-224
+                }
                 if (r.always_pass) continue;                // cluster rule, no fallback (:184-193)
                 const int sel = xflow_select(st, r, r0, r1, origin, ctx);
                 if (sel == XS_NONE) continue;
@@ -300,20 +319,22 @@ SF_HD void xg_event(const DevState& st, const SegIO& io, const ParamTable& pt, u
 // in registers while consecutive events use them (a group of one resource
 // keeps its node for the whole segment); a switch stores the old node back
 // first, so a RELATE read of another member always sees HBM up to date.
-template <int MAXS>
+template <int MAXS, bool EMB = false>
 SF_HD void decide_xgroup(const DevState& st, const SegIO& io, uint32_t lo, uint32_t hi) {
     const ParamTable pt{st.ptab, st.pcap_mask, st.err, st.pins};
     NodeWin<MAXS> cn, on, dn;
     uint32_t cl = XNONE, oi = XNONE, di = XNONE;          // nodes held in cn / on / dn
-    for (uint32_t j = lo; j < hi; j++) xg_event<MAXS>(st, io, pt, lo, j, cn, on, dn, cl, oi, di);
+    for (uint32_t j = lo; j < hi; j++) xg_event<MAXS, EMB>(st, io, pt, lo, j, cn, on, dn, cl, oi, di);
     if (cl != XNONE) nw_store(cn, st, cluster_rows(st, cl));
     if (oi != XNONE) nw_store(on, st, aux_rows(st, oi));
     if (di != XNONE) nw_store(dn, st, aux_rows(st, di));
 }
 
 // ============================================================ wave walk eligibility
-enum : uint8_t { XWF_ON = 1, XWF_THREAD = 2 };
+enum : uint8_t { XWF_ON = 1, XWF_THREAD = 2, XWF_CL = 4 };
 constexpr uint32_t XW_MIN = 256;               // shorter xflow segments stay on k_decide_x's lanes
+constexpr uint32_t XCL_MIN = 256;              // ... and shorter bound-rule segments (k_decide_xcl; never below XW_MIN:
+                                               // both kinds share the bound of Work::xw_list / xcl_list)
 // a segment of resource l (its own group) with all-DIRECT rules, no ParamFlow
 // rule and no circuit breaker, at least XW_MIN events: k_decide_xw
 SF_HD bool xw_take(const DevState& st, uint32_t l, uint32_t len) {
@@ -324,11 +345,25 @@ SF_HD bool xw_take(const DevState& st, uint32_t l, uint32_t len) {
     return b0 == b1;
 }
 
+// a segment of resource l (its own group) whose only flow rule is a bound
+// DIRECT cluster rule with a loaded flowId outside any limiter namespace (XWF_CL,
+// build_xw), no ParamFlow rule and no circuit breaker, at least xcl_min events:
+// k_decide_xcl (sf_xcluster.hip)
+SF_HD bool xcl_take(const DevState& st, uint32_t l, uint32_t len) {
+    if (!st.emb || !st.xw || !(st.xw[l] & XWF_CL) || len < st.emb->xcl_min) return false;
+    if (st.prule_off[l + 1] != st.prule_off[l]) return false;
+    uint32_t b0, b1;
+    breakers_of(st, l, &b0, &b1);
+    return b0 == b1;
+}
+
 // ============================================================ groups (host side)
 // xw[l] for the resources of one-member groups whose rules all check DIRECT
 // (their ClusterNode or an origin node: no RELATE / CHAIN)
+// (a resource with a bound cluster rule never takes k_decide_xw: bind, as for build_xmap;
+// XWF_CL instead when k_decide_xcl may take its segments, see xcl_take)
 inline void build_xw(const DevRule* dr, const uint32_t* off, uint32_t R, const std::vector<uint32_t>& xmap,
-                     std::vector<uint8_t>& xw) {
+                     std::vector<uint8_t>& xw, const int64_t* bind = nullptr, const uint8_t* bind_wave = nullptr) {
     xw.assign(R, 0);
     std::vector<uint32_t> members(R, 0);
     for (uint32_t l = 0; l < R; l++)
@@ -337,10 +372,16 @@ inline void build_xw(const DevRule* dr, const uint32_t* off, uint32_t R, const s
         if (xmap[l] != l || members[l] != 1) continue;
         uint8_t f = XWF_ON;
         for (uint32_t k = off[l]; k < off[l + 1]; k++) {
-            if (dr[k].strategy != SF_STRATEGY_DIRECT) { f = 0; break; }
+            if (dr[k].strategy != SF_STRATEGY_DIRECT || (bind && bind[k] != 0)) { f = 0; break; }
             if (dr[k].grade == SF_GRADE_THREAD) f |= XWF_THREAD;
         }
         xw[l] = f;
+        // bind_wave[k]: bound rule k's flowId is loaded and its namespace has no limiter
+        // and the rule is DIRECT: a CHAIN rule keeps a context DefaultNode that every entry is accounted on
+        // (xg_event's want_dn), and RELATE names another resource; those stay on the lane
+        if (bind_wave && off[l + 1] - off[l] == 1 && bind[off[l]] != 0 && bind_wave[off[l]] &&
+            dr[off[l]].strategy == SF_STRATEGY_DIRECT)
+            xw[l] = XWF_CL;
     }
 }
 
@@ -352,9 +393,17 @@ inline bool rule_is_ext(const DevRule& r) {
 // xmap[l] = key of l's group (its smallest member; members: resources with an
 // extended rule and the resources RELATE rules read, joined by RELATE), XNONE
 // elsewhere.  Returns false (xmap untouched) when no rule is extended.
-inline bool build_xmap(const DevRule* dr, const uint32_t* off, uint32_t R, std::vector<uint32_t>& xmap) {
+// Embedded token server: bind[k] != 0 is the flowId of bound rule k (CSR
+// position), bind_ns[k] its namespace index when that namespace has a
+// GlobalRequestLimiter, else -1.  A resource with a bound rule is a member.
+// The limiter is one sequential gate over its namespace
+// (GlobalRequestLimiter.java:46-55) and a flowId has one ClusterMetric, so the
+// resources bound into one limiter namespace, and the resources bound to one
+// flowId, are joined: one lane replays them in submission order.
+inline bool build_xmap(const DevRule* dr, const uint32_t* off, uint32_t R, std::vector<uint32_t>& xmap,
+                       const int64_t* bind = nullptr, const int32_t* bind_ns = nullptr) {
     bool any = false;
-    for (uint32_t k = 0; k < off[R] && !any; k++) any = rule_is_ext(dr[k]);
+    for (uint32_t k = 0; k < off[R] && !any; k++) any = rule_is_ext(dr[k]) || (bind && bind[k] != 0);
     if (!any) return false;
     std::vector<uint32_t> par(R, XNONE);
     auto find = [&](uint32_t x) {
@@ -365,11 +414,22 @@ inline bool build_xmap(const DevRule* dr, const uint32_t* off, uint32_t R, std::
         a = find(a); b = find(b);
         if (a != b) { if (a < b) par[b] = a; else par[a] = b; }   // the root is the smallest member
     };
+    std::unordered_map<int64_t, uint32_t> by_flow;     // flowId / limiter namespace -> a resource bound to it
+    std::unordered_map<int32_t, uint32_t> by_ns;
     for (uint32_t l = 0; l < R; l++)
         for (uint32_t k = off[l]; k < off[l + 1]; k++) {
             const DevRule& r = dr[k];
-            if (!rule_is_ext(r)) continue;
+            const bool bound = bind && bind[k] != 0;
+            if (!rule_is_ext(r) && !bound) continue;
             if (par[l] == XNONE) par[l] = l;
+            if (bound) {
+                auto it = by_flow.emplace(bind[k], l);
+                if (!it.second) join(l, it.first->second);
+                if (bind_ns && bind_ns[k] >= 0) {
+                    auto jt = by_ns.emplace(bind_ns[k], l);
+                    if (!jt.second) join(l, jt.first->second);
+                }
+            }
             if (r.strategy == SF_STRATEGY_RELATE && r.ref != XNONE && r.ref < R) {
                 if (par[r.ref] == XNONE) par[r.ref] = r.ref;
                 join(l, r.ref);

@@ -75,6 +75,7 @@ def _declare(L):
     f("sf_load_namespaces", I, P, C.POINTER(abi.sf_namespace), U32)
     f("sf_load_cluster_rules", I, P, C.POINTER(abi.sf_cluster_flow_rule), U32,
       C.POINTER(abi.sf_cluster_param_rule), U32, C.POINTER(abi.sf_hot_item), U32)
+    f("sf_load_cluster_binds", I, P, C.POINTER(abi.sf_cluster_bind), U32)
     f("sf_request_tokens", I, P, C.POINTER(abi.sf_token_batch), C.POINTER(abi.sf_token_results))
     f("sf_load_concurrent_config", I, P, C.POINTER(abi.sf_concurrent_config), U32)
     f("sf_concurrent_reserve", I, P, C.c_uint64)
@@ -755,6 +756,16 @@ class FlowEngine:
         _check(lib().sf_load_cluster_rules(self.h, abi.rules_array(abi.sf_cluster_flow_rule, list(flow)), len(flow),
                                            abi.rules_array(abi.sf_cluster_param_rule, list(param)), len(param),
                                            abi.rules_array(abi.sf_hot_item, list(items)), len(items)))
+
+    def load_cluster_binds(self, binds=()):
+        """Embedded token server: ``binds`` is a list of (rule_index, flow_id); the cluster-mode flow
+        rule at ``rule_index`` of the list last given to load_flow_rules takes its tokens from this
+        engine's token server inside submit (sf_load_cluster_binds).  An empty list clears the table;
+        load_flow_rules clears it too."""
+        arr = (abi.sf_cluster_bind * max(1, len(binds)))()
+        for i, (k, fid) in enumerate(binds):
+            arr[i].rule_index, arr[i].flow_id = k, fid
+        _check(lib().sf_load_cluster_binds(self.h, arr, len(binds)))
 
     def request_tokens(self, batch: abi.HostTokenBatch) -> abi.HostTokenResults:
         out = abi.HostTokenResults(batch.n)
